@@ -11,6 +11,9 @@ Metric (BASELINE.json): self-play env-steps/s (+ MCTS sims/s), det-MADN batch 40
 Weak scaling: every rank plays its own 4096 games (games are independent; no data-path collective).
 Timing: W untimed warm-up steps, then K steps between barrier + synchronize on both sides,
 max over ranks.  Rank 0 prints ONE JSON line.
+A plain run does only that (set up, W warm-up steps, K timed steps, the line); --full adds the measurements
+that take runs of their own after the timed steps (the CPU baseline, det's one-batch figure), and
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 
 Weights are seeded random (Flax-default init; no checkpoints are available), data is synthetic
 (self-generated games), arithmetic is fp32 end to end (the north star's 1e-5 fp32 target).
@@ -90,7 +93,17 @@ def parse():
     ap.add_argument("--depth", type=int, default=None, help="MCTS max depth (det / classic 25, dog muzero 50)")
     ap.add_argument("--max-steps", type=int, default=MAX_STEPS)
     ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU-baseline sample (1 core + all cores)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU-baseline sample")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also take the secondary measurements, each a run of its own: the CPU "
+                         "baseline (cpu_baseline; --no-cpu-baseline leaves it out) and, for det, one play_n_games_v3 "
+                         "batch to completion (single_batch / value_single_batch).  A plain run sets up, warms up, "
+                         "times the steps and prints the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="det / classic: after the timed steps write what the last timed step returned -- the "
+                         "self-play record buffers of its games, rows past a game's idx as the reference initialises "
+                         "them -- as DIR/<name>.npy in float32: idx of every game, the other fields for a fixed seeded "
+                         "sample of the games (at most 64 MB in all).  Rank 0's games at N > 1")
     ap.add_argument("--games", type=int, default=-1,
                     help="det: games per step streamed through the --batch lanes (default 32 x batch; 0 = one "
                          "batch of --batch games, the reference's play_n_games_v3 call)")
@@ -125,6 +138,10 @@ def parse():
         args.sims = DOG_MZ_SIMS if dog_mz else S
     if args.depth is None:
         args.depth = DOG_MZ_DEPTH if dog_mz else D
+    if args.dump_outputs and args.workload not in ("det", "classic"):
+        raise SystemExit(f"--dump-outputs: the {args.workload} workload returns no record buffers to write")
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
     args.job_batch = args.batch
     if args.split:
         world = int(os.environ.get("WORLD_SIZE", str(args.gpus)))
@@ -359,6 +376,40 @@ def timed_region(dist, fn, steps):
     return time.perf_counter() - t0
 
 
+DUMP_GAMES = 256        # --dump-outputs: games sampled for the per-turn fields
+DUMP_OBS_GAMES = 16     # ... and for obs, the one large field (2 MB per det game as float32)
+
+
+def dump_selfplay_outputs(path, buf):
+    """--dump-outputs: the record buffers the last timed step returned (game_agent.SelfPlayEngine.play / play_stream
+    or the stochastic engine's: obs, act, rew, val, pol, mask, player, team, discount, idx) as <path>/<name>.npy in
+    float32.  idx of every game; the other fields for DUMP_GAMES games drawn once with a fixed seed (obs for the first
+    DUMP_OBS_GAMES of them), the same games for the same arguments.  The engines write only rows below a game's idx,
+    so rows at or past it are set as the reference initialises them (zeros, team -1; game_agent.reference_buffers)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    n, T = buf["act"].shape[0], buf["act"].shape[1]
+    pick = np.sort(np.random.RandomState(0).permutation(n)[:DUMP_GAMES])
+    sel = torch.from_numpy(pick).to(buf["idx"].device)
+    idx = buf["idx"].index_select(0, sel).long()
+    past = torch.arange(T, device=idx.device)[None, :] >= idx[:, None]
+    total = 0
+    for k, v in buf.items():
+        if k == "idx":
+            x = v.to(torch.float32)
+        else:
+            # obs takes at most half of the 64 MB (4p classic games are 3.8 MB each)
+            m = max(1, min(DUMP_OBS_GAMES, (32 << 20) // (4 * v[0].numel()))) if k == "obs" else len(pick)
+            x = torch.stack([v[int(g)] for g in pick[:m]]).to(torch.float32)   # per-game views: obs is > 2^31 elements
+            x.masked_fill_(past[:m].view(past[:m].shape + (1,) * (x.dim() - 2)), -1.0 if k == "team" else 0.0)
+        a = x.cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, f"{k}.npy"), a)
+    assert total <= 64 << 20, total
+    beat(f"--dump-outputs: {len(buf)} arrays, {total / 2**20:.1f} MiB in {path}")
+
+
 def sum_max(dist, device, sums, elapsed):
     """Sum work over ranks, max of wall time (the slowest rank bounds the job)."""
     import torch
@@ -544,7 +595,7 @@ def run_dog_muzero(args):
                              f"{args.batch} games occupy {-(-args.batch // gpw)} of the 256 CUs; a workgroup's "
                              f"search time is its serial chain of 100 simulations"},
     }
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = dog_muzero_cpu_baseline(args.cpu_seconds, args.sims, args.depth)
     print(json.dumps(out), flush=True)
     if dist is not None:
@@ -620,7 +671,7 @@ def run_dog(args):
     }
     if args.records:
         out["records_gathered"] = int(gathered[0])
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = dog_cpu_baseline(min(args.cpu_seconds, 15.0))
     print(json.dumps(out), flush=True)
     if dist is not None:
@@ -673,10 +724,10 @@ def run_classic(args):
     for w in range(args.warmup):
         play(10_000 * rank + w)
         beat(f"warm-up {w + 1}/{args.warmup}")
-    acc = {"steps": 0, "searches": 0, "search_ms": 0.0, "turns": 0}
+    acc = {"steps": 0, "searches": 0, "search_ms": 0.0, "turns": 0, "buf": None}
 
     def step(k):
-        buf = play(10_000 * rank + 1000 + k)
+        buf = acc["buf"] = play(10_000 * rank + 1000 + k)
         st = eng.last_stats
         acc["steps"] += int(buf["idx"].sum().item())
         acc["searches"] += st["searches"]
@@ -686,6 +737,8 @@ def run_classic(args):
     elapsed = timed_region(dist, step, args.steps)
     (steps_done, searches, search_ms, turns), elapsed = sum_max(
         dist, device, [acc["steps"], acc["searches"], acc["search_ms"], acc["turns"]], elapsed)
+    if args.dump_outputs and rank == 0:
+        dump_selfplay_outputs(args.dump_outputs, acc["buf"])
     if rank != 0:
         if dist is not None:
             dist.destroy_process_group()
@@ -714,7 +767,7 @@ def run_classic(args):
     out["roofline"].update({"traffic": None if traffic is None else round(traffic),
                             "traffic_achieved_tbs": None if traffic is None or avg_s <= 0 else
                             round(traffic / avg_s / 1e12, 3), "traffic_source": traffic_src})
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = classic_cpu_baseline(min(args.cpu_seconds, 20.0), args.sims, args.depth, args.max_steps)
     print(json.dumps(out), flush=True)
     if dist is not None:
@@ -1019,7 +1072,7 @@ def run_env(args):
     if traffic:
         out["roofline"].update(traffic=round(traffic), traffic_unit="bytes/launch (HBM, PMC)", traffic_source=src,
                                traffic_over_algorithmic=round(traffic / (B * per), 3))
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         from oracle import cpu_selfplay as CS
         cores, aff = cpu_cores()
         half = min(args.cpu_seconds, 20.0) / 2
@@ -1082,10 +1135,10 @@ def run_det(args):
         play(10_000 * rank + w)
         beat(f"warm-up {w + 1}/{args.warmup}")
     torch.cuda.synchronize()
-    acc = {"steps": 0, "searches": 0, "search_ms": 0.0, "launches": 0}
+    acc = {"steps": 0, "searches": 0, "search_ms": 0.0, "launches": 0, "buf": None}
 
     def step(k):
-        buf = play(10_000 * rank + 1000 + k)
+        buf = acc["buf"] = play(10_000 * rank + 1000 + k)
         st = eng.last_stats
         acc["steps"] += int(buf["idx"].sum().item())
         acc["searches"] += st["searches"]
@@ -1095,15 +1148,17 @@ def run_det(args):
     elapsed = timed_region(dist, step, args.steps)
     (steps_done, searches, search_ms, launches), elapsed = sum_max(
         dist, device, [acc["steps"], acc["searches"], acc["search_ms"], acc["launches"]], elapsed)
-    # Secondary figure in the reference's own loop shape (game_agent.py:185-192): ONE play_n_games_v3 batch of
-    # --batch games per rank played to completion (the batch shrinks as games finish), timed on its own after
+    if args.dump_outputs and rank == 0:       # before anything else plays into the engine's buffers
+        dump_selfplay_outputs(args.dump_outputs, acc["buf"])
+    # --full: secondary figure in the reference's own loop shape (game_agent.py:185-192): ONE play_n_games_v3 batch
+    # of --batch games per rank played to completion (the batch shrinks as games finish), timed on its own after
     # the K streamed steps; `value` stays the streamed rate.
     single = {"steps": 0}
 
     def single_batch(_):
         single["steps"] += int(eng.play(seed=10_000 * rank + 999, temperature=TEMP)["idx"].sum().item())
 
-    single_elapsed = timed_region(dist, single_batch, 1) if args.games else None
+    single_elapsed = timed_region(dist, single_batch, 1) if args.games and args.full else None
     if single_elapsed is not None:
         (single_steps,), single_elapsed = sum_max(dist, device, [single["steps"]], single_elapsed)
     if rank != 0:
@@ -1137,12 +1192,6 @@ def run_det(args):
                    "num_simulations": args.sims, "max_depth": args.depth,
                    "parallelism": parallelism(args, world)},
         "sims_per_s": round(searches * args.sims / elapsed, 1),
-        "value_single_batch": (round(single_steps / single_elapsed, 2) if single_elapsed else round(value, 2)),
-        "single_batch": ({"games_per_gpu": args.batch, "env_steps": int(single_steps),
-                          "seconds": round(single_elapsed, 4), "unit": "env_steps/s",
-                          "what": "one play_n_games_v3 batch per rank to completion (game_agent.py:185-192), "
-                                  "timed after the streamed steps"} if single_elapsed else
-                         {"what": "--games 0: value itself is the single-batch rate"}),
         "env_steps": int(steps_done),
         "searches": int(searches),
         "roofline": {"bound": "mfma", "kernel": "k_gumbel_search", "achieved": round(achieved, 3),
@@ -1172,7 +1221,14 @@ def run_det(args):
     loop = measured_loop_ceiling()
     if loop:
         out["roofline"]["loop_ceiling"] = dict(loop, frac_of_ceiling=round(achieved / PEAK_FP32_MFMA_TFLOPS / loop["frac"], 4))
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full:
+        out["value_single_batch"] = round(single_steps / single_elapsed, 2) if single_elapsed else round(value, 2)
+        out["single_batch"] = ({"games_per_gpu": args.batch, "env_steps": int(single_steps),
+                                "seconds": round(single_elapsed, 4), "unit": "env_steps/s",
+                                "what": "one play_n_games_v3 batch per rank to completion (game_agent.py:185-192), "
+                                        "timed after the streamed steps"} if single_elapsed else
+                               {"what": "--games 0: value itself is the single-batch rate"})
+    if world == 1 and args.full and not args.no_cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args.cpu_seconds, args.sims, args.depth, args.max_steps)
     print(json.dumps(out), flush=True)
     if dist is not None:

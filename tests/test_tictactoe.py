@@ -87,7 +87,8 @@ import json  # noqa: E402
 import os  # noqa: E402
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-REF_CKPT = "/root/reference/TicTacToe/Checkpoints/TicTacToeV2_imp_net_3000ep_00001lr.params"
+# the reference's TicTacToe/Checkpoints/TicTacToeV2_imp_net_3000ep_00001lr.params (Flax msgpack weights), stored as is
+REF_CKPT = os.path.join(GOLDEN, "ttt_imp_net_3000ep.params")
 
 
 def _ck():
@@ -97,7 +98,6 @@ def _ck():
     return CK
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CKPT), reason="reference checkpoint not present")
 def test_flax_msgpack_roundtrip_is_byte_exact():
     CK = _ck()
     raw = open(REF_CKPT, "rb").read()
