@@ -17,18 +17,16 @@
 //    806 prior logits going from the logits chunks straight into the new node's children.
 #define MUZ_OPAQUE_TID 1   // (nn.hpp tid())
 #include "dog_nets.hpp"
-#include "launch.hpp"
 #include "rng.hpp"
+#include "tree.hpp"
 
 namespace muz {
 
 constexpr int kWJ = 26;                      // child slots per lane
 constexpr int kWPad = kRowLanes * kWJ;       // 832 children per node
-constexpr int kWMaxSims = 100, kWMaxNodes = kWMaxSims + 1, kWMaxDepth = 64;
 constexpr int kWWords = 26;                  // legal mask words (MUZ_DOG_MASK_WORDS)
-constexpr float kWFMin = -3.4028234663852886e38f;
 static_assert(kRowLanes == 32, "one game per 32 lanes");
-static_assert(kWMaxSims <= 255, "visit counts in 8 bits (WNode::vis4)");
+static_assert(kMaxSims <= 255, "visit counts in 8 bits (WNode::vis4)");
 static_assert(kWPad >= kDogA && kWWords * 32 >= kDogA, "slots");
 static_assert(2 * kRows * kDogA <= kArenaFloats, "the walk's per-child arrays live in the idle network arena");
 
@@ -117,10 +115,6 @@ static WTree carve_wide(void* ws, int n, int N) {
   return t;
 }
 
-// exp correctly rounded (float64, rounded once): oracle/mctx_gumbel.py exp_cr, search.hip exp_cr
-// (A/B, profiles/r4k_dog_ab.log: a float __expf in its place -- wrong rounding -- was 22-27 % faster per search)
-__device__ __forceinline__ float exp_cr_w(float x) { return (float)exp((double)x); }
-
 // sum of this game's 806 entries f(j) (this lane's slot j; padding slots give -0) in the lane order of
 // oracle/mctx_gumbel.py lane_tree_sum: each lane its slots in turn, then a balanced tree over the 32 lanes
 template <class F>
@@ -134,29 +128,9 @@ __device__ __forceinline__ float wsum(F f) {
   return row_sum(s);   // xor1, xor2, half mirror, mirror, swap16: the balanced tree in lane order
 }
 
-// argmax over the row's 806 children of score f(j) (this lane's slot j), jnp.argmax tie-break (first index):
-// this lane's slots in ascending order (strict >), then row_argmax's (value, index) order across the lanes.
-// Streams the scores: no per-slot array is kept.
-// (value, index) argmax across the row's lanes, row_argmax's order (larger value, then smaller index)
-__device__ __forceinline__ void wargmax_row2(float& v, int& i) {
-  auto pick = [](float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  };
-  pick(v, i, dpp<DPP_XOR1>(v), dpp<DPP_XOR1>(i));
-  pick(v, i, dpp<DPP_XOR2>(v), dpp<DPP_XOR2>(i));
-  pick(v, i, dpp<DPP_HALF_MIRROR>(v), dpp<DPP_HALF_MIRROR>(i));
-  pick(v, i, dpp<DPP_MIRROR>(v), dpp<DPP_MIRROR>(i));
-  const LoHi<float> pv = swap16(v);
-  const LoHi<int> pi = swap16(i);
-  v = pv.lo;
-  i = pi.lo;
-  pick(v, i, pv.hi, pi.hi);
-}
+// the index of the row's (value, index) argmax (row_argmax, tree.hpp)
 __device__ __forceinline__ int wargmax_row(float v, int i) {
-  wargmax_row2(v, i);
+  row_argmax(v, i);
   return i;
 }
 
@@ -208,24 +182,6 @@ __device__ __forceinline__ int wroot_argmax(const WTree& T, int g, int sub, cons
 }
 
 __device__ __forceinline__ bool wok(int sub, int j) { return sub + kRowLanes * j < kDogA; }
-
-// seq_halving.get_sequence_of_considered_visits(m, S)[idx] (search.hip considered_visit)
-__device__ __forceinline__ int wconsidered_visit(int m, int S, int idx) {
-  if (m <= 1) return idx;
-  int log2max = 0;
-  while ((1 << log2max) < m) ++log2max;
-  int k = m, v = 0, len = 0;
-  while (len < S) {
-    const int extra = max(1, S / (log2max * k));
-    for (int e = 0; e < extra; ++e) {
-      if (idx < len + k) return v;
-      len += k;
-      ++v;
-    }
-    k = max(2, k / 2);
-  }
-  return v;
-}
 
 // One node's children in this lane's slots + qtransform_completed_by_mix_value (value_scale, maxvisit_init,
 // rescale, mixed value, eps 1e-8): pr = prior logits, cq = the transformed completed Q (both in LDS: the tile's
@@ -335,7 +291,7 @@ __device__ __forceinline__ void wnode_full(WNode& nd, const WTree& T, int g, int
   ST(ST_OTHER);   // (diagnostic builds)
   if (es < 0.f) {   // (row-uniform)
     st_count(12);   // (diagnostic builds: first walks)
-    es = wsum([&](int j) { return wok(sub, j) ? exp_cr_w(nd.pr[sub + kRowLanes * j] - pm) : -0.0f; });
+    es = wsum([&](int j) { return wok(sub, j) ? exp_cr(nd.pr[sub + kRowLanes * j] - pm) : -0.0f; });
     if (sub == 0) ces[node] = es;
     // the kWTop largest priors in (value desc, index asc) order, one row argmax after another
     float pv = INFINITY;
@@ -355,7 +311,7 @@ __device__ __forceinline__ void wnode_full(WNode& nd, const WTree& T, int g, int
           }
         }
       }
-      wargmax_row2(v, i);
+      row_argmax(v, i);
       if (sub == r) {
         T.tp(g, node)[r] = v;
         T.ti(g, node)[r] = i;
@@ -446,7 +402,7 @@ __device__ __forceinline__ bool wnode_compact(WNode& nd, const WTree& T, int g, 
   // wnode_tail<true>.
   if (en.a >= 0) {
     if (en.e != en.e) {
-      en.e = exp_cr_w(en.p - nd.pm);
+      en.e = exp_cr(en.p - nd.pm);
       tree_st(reinterpret_cast<AS1 float*>(T.vr(g, node) + 2 * sub + 1) + 3, en.e);
     }
     nd.pr[en.a] = en.e;
@@ -471,7 +427,7 @@ __device__ __forceinline__ void wnode_tail(WNode& nd, int sub, float raw, const 
 #pragma clang fp contract(off)
   const float pm = nd.pm, es = nd.es;
   const unsigned vm = nd.vm;
-  auto ppa = [&](int a) { return fmaxf(kTinyF, (exps ? nd.pr[a] : exp_cr_w(nd.pr[a] - pm)) / es); };
+  auto ppa = [&](int a) { return fmaxf(kTinyF, (exps ? nd.pr[a] : exp_cr(nd.pr[a] - pm)) / es); };
   float spl = 0.f;
   for (unsigned m = vm; m; m &= m - 1u) spl = spl + ppa(sub + kRowLanes * (__ffs(m) - 1));
   const float sp = row_sum(spl);
@@ -510,7 +466,7 @@ __device__ __forceinline__ void wentries(const WNode& nd, const WTree& T, int g,
   if (en.a >= 0) {
     en.p = nd.pr[en.a];
     en.c = nd.cq[en.a];
-    en.e = exp_cr_w(en.p - nd.pm);
+    en.e = exp_cr(en.p - nd.pm);
     // (the record's prior and cached exponential refreshed: the node's priors change when it is expanded again at
     // the depth limit)
     tree_st(reinterpret_cast<AS1 float*>(T.vr(g, node) + 2 * sub) + 2, en.p);
@@ -542,9 +498,9 @@ __device__ __forceinline__ int wselect_certified(const WNode& nd, const WEntry& 
   const bool has = en.a >= 0;
   const float z = has ? en.p + en.c : -INFINITY;
   const float zm = fmaxf(row_max(z), zU);   // fl(p + K) is monotone in p: zU is the unvisited maximum
-  const float ez = has ? exp_cr_w(z - zm) : 0.f;
+  const float ez = has ? exp_cr(z - zm) : 0.f;
   const float sez = row_sum(ez);
-  const float sep = row_sum(has ? en.e : 0.f);   // en.e = exp_cr_w(en.p - nd.pm) (wnode_compact / wentries)
+  const float sep = row_sum(has ? en.e : 0.f);   // en.e = exp_cr(en.p - nd.pm) (wnode_compact / wentries)
   const double f = exp((double)K + (double)nd.pm - (double)zm);
   const double zsa = (double)sez + f * fmax((double)nd.es - (double)sep, 0.0);
   // per-element relative error of the argument roundings <= 2^-24 (c0 + 3 d) e^-d summed (d e^-d <= 1/e over 806
@@ -558,8 +514,8 @@ __device__ __forceinline__ int wselect_certified(const WNode& nd, const WEntry& 
   // the best visited candidate of the row by lower bound
   float blo = has ? (ez / zhi - n) - slack : -INFINITY;
   int bi = has ? en.a : kDogA;
-  wargmax_row2(blo, bi);
-  const float ezU = exp_cr_w(zU - zm);
+  row_argmax(blo, bi);
+  const float ezU = exp_cr(zU - zm);
   const float loU = ezU / zhi - 0x1p-20f * (ezU / zlo), hiU = ezU / zlo + 0x1p-20f * (ezU / zlo);
   const bool pick_u = loU > blo || bi >= kDogA;
   if (pick_u) {
@@ -567,7 +523,7 @@ __device__ __forceinline__ int wselect_certified(const WNode& nd, const WEntry& 
     blo = loU;
     if (!(loU > 0x1p-100f)) return -1;   // (normal range: the ulp argument below holds)
     // no other unvisited child may reach u1's score: its exponential more than 4 ulps above the runner-up's
-    if (nd.u2 != -INFINITY && !(ezU > exp_cr_w((nd.u2 + K) - zm) * (1.f + 0x1p-21f))) return -1;
+    if (nd.u2 != -INFINITY && !(ezU > exp_cr((nd.u2 + K) - zm) * (1.f + 0x1p-21f))) return -1;
   }
   // upper bounds of every other candidate
   const float hub = fmaxf(row_max(has && en.a != bi ? (q_hi - n) + slack : -INFINITY), pick_u ? -INFINITY : hiU);
@@ -603,18 +559,18 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
 #pragma clang fp contract(off)
   (void)Wt;
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
-  __shared__ int s_visits[kRows][kWMaxNodes];
-  __shared__ float s_raw[kRows][kWMaxNodes];
-  __shared__ float s_val[kRows][kWMaxNodes];
-  __shared__ int p_node[kRows][kWMaxDepth];
-  __shared__ int p_act[kRows][kWMaxDepth];
-  __shared__ int p_cvis[kRows][kWMaxDepth];
-  __shared__ float p_rew[kRows][kWMaxDepth];
-  __shared__ float p_disc[kRows][kWMaxDepth];
-  __shared__ float p_prior[kRows][kWMaxDepth];
+  __shared__ int s_visits[kRows][kMaxNodes];
+  __shared__ float s_raw[kRows][kMaxNodes];
+  __shared__ float s_val[kRows][kMaxNodes];
+  __shared__ int p_node[kRows][kMaxDepth];
+  __shared__ int p_act[kRows][kMaxDepth];
+  __shared__ int p_cvis[kRows][kMaxDepth];
+  __shared__ float p_rew[kRows][kMaxDepth];
+  __shared__ float p_disc[kRows][kMaxDepth];
+  __shared__ float p_prior[kRows][kMaxDepth];
   __shared__ uint32_t s_legal[kRows][kWWords];
-  __shared__ float s_ces[kRows][kWMaxNodes];   // per-node softmax normalisers of the priors (wnode_full)
-  __shared__ signed char s_vcnt[kRows][kWMaxNodes];   // per-node visited-list lengths (-1: overflowed)
+  __shared__ float s_ces[kRows][kMaxNodes];   // per-node softmax normalisers of the priors (wnode_full)
+  __shared__ signed char s_vcnt[kRows][kMaxNodes];   // per-node visited-list lengths (-1: overflowed)
   __shared__ int s_act[kRows], s_parent[kRows], s_next[kRows], s_depth[kRows];
 
   const int kGames = SPARSE ? sa.games_per_wg : kRows;   // games per workgroup
@@ -650,10 +606,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
 #pragma unroll
     for (int j = 0; j < kWJ; ++j) {
       const int a = sub + kRowLanes * j;
-      pr[j] = kWFMin;
+      pr[j] = kFMin;
       if (a < kDogA) {
         const bool inv = ((legal[(size_t)g * kWWords + j] >> sub) & 1u) == 0u;
-        pr[j] = inv ? kWFMin : root_logits[(size_t)g * kDogA + a] - lm;
+        pr[j] = inv ? kFMin : root_logits[(size_t)g * kDogA + a] - lm;
         pm = fmaxf(pm, pr[j]);
         tree_st(T.prior() + T.ca(g, 0, a), pr[j]);
       }
@@ -669,7 +625,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
         gpw(T.gum)[(size_t)g * kWPad + a] = gm + (pr[j] - pm);
       }
     }
-    for (int i = sub; i < kWMaxNodes; i += kRowLanes) {
+    for (int i = sub; i < kMaxNodes; i += kRowLanes) {
       s_ces[row][i] = -1.f;
       s_vcnt[row][i] = 0;
     }
@@ -719,7 +675,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
           wnode_tail(nd, sub, s_raw[row][node], sa, compact);
           if (depth == 0) {
             // gumbel_muzero_root_action_selection: score_considered + masked_argmax
-            const int cv = wconsidered_visit(ncons, sa.S, nd.sv);
+            const int cv = considered_visit(ncons, sa.S, nd.sv);
             wfill_unvisited(nd, sub);
             bi = wroot_argmax(T, g, sub, nd.cq, [&](int j) { return nd.vis(j); }, cv, legal_of);
           } else if (pass == 0 && (bi = wselect_interior(nd, en, T, g, node, sub, vc, compact, sa.exact_select)) >= 0) {
@@ -745,7 +701,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
             const float zs = wsum([&](int j) {
               const int a = sub + kRowLanes * j;
               if (a >= kDogA) return -0.0f;
-              const float ez = exp_cr_w(nd.pr[a] - zm);
+              const float ez = exp_cr(nd.pr[a] - zm);
               nd.pr[a] = ez;
               return ez;
             });
@@ -849,8 +805,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
         if (fresh) s_vcnt[row][nx] = 0;
         s_visits[row][nx] = fresh ? 1 : s_visits[row][nx] + 1;
       }
-      // ---------------- backward along the recorded path, one level per lane (search.hip's scheme; the root's
-      // edges are tree entries here)
+      // ---------------- backward along the recorded path, one level per lane: backup_lanes' scheme (tree.hpp) with
+      // this kernel's edge and visited-record writes; the root's edges are tree entries here.  Written out here
+      // because through the shared template this kernel measured 1.4 % slower per DOG self-play step (3 spills
+      // instead of 9, but 25-28 instructions more and another schedule)
       const int d = s_depth[row];
       float carry = v, carry_v = v;
       for (int base = ((d - 1) / kRowLanes) * kRowLanes; base >= 0; base -= kRowLanes) {
@@ -937,7 +895,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
     for (int j = 0; j < kWJ; ++j) {
       const int a = sub + kRowLanes * j;
       if (a < kDogA) {
-        const float zz = !legal_of(j) ? kWFMin : (nd.pr[a] + nd.cq[a]) - zm;
+        const float zz = !legal_of(j) ? kFMin : (nd.pr[a] + nd.cq[a]) - zm;
         nd.pr[a] = zz;
         mm = fmaxf(mm, zz);
       }
@@ -946,7 +904,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_dog_search(muz_dog_net_w Wt, Se
     const float zs = wsum([&](int j) {
       const int a = sub + kRowLanes * j;
       if (a >= kDogA) return -0.0f;
-      const float ez = exp_cr_w(nd.pr[a] - mm);
+      const float ez = exp_cr(nd.pr[a] - mm);
       nd.pr[a] = ez;
       return ez;
     });
@@ -1021,22 +979,13 @@ int muz_dog_gumbel_search(const muz_dog_net_w* w, const muz_search_cfg* cfg, con
   int rc = check_dog_net(w);
   if (rc) return rc;
   if (!cfg) return MUZ_E_INVALID;
-  if (cfg->num_simulations < 1 || cfg->num_simulations > kWMaxSims) return MUZ_E_UNSUPPORTED;
-  if (cfg->max_depth < 1 || cfg->max_depth > kWMaxDepth) return MUZ_E_UNSUPPORTED;
+  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
   if (cfg->max_num_considered < 1) return MUZ_E_UNSUPPORTED;
   MUZ_HOST_CHECK(n >= 0 && root_logits && root_value && root_embedding && legal && workspace && action &&
                  action_weights && root_value_out);
   MUZ_HOST_CHECK(workspace_bytes >= dog_search_workspace_bytes(n, cfg->num_simulations));
   if (n == 0) return MUZ_OK;
-  SearchArgs sa;
-  sa.S = cfg->num_simulations;
-  sa.D = cfg->max_depth;
-  sa.max_considered = cfg->max_num_considered;
-  sa.value_scale = cfg->value_scale;
-  sa.maxvisit_init = cfg->maxvisit_init;
-  sa.gumbel_scale = cfg->gumbel_scale;
-  sa.seed = cfg->seed;
-  sa.turn = cfg->turn;
+  SearchArgs sa = make_search_args(*cfg);
   {   // MUZ_DOG_EXACT_SELECT=1: every interior selection on the exact path (tests of that path)
     const char* e = getenv("MUZ_DOG_EXACT_SELECT");
     sa.exact_select = e && e[0] == '1';

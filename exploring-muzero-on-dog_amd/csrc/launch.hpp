@@ -6,6 +6,15 @@
 
 namespace muz {
 
+// The limits every search kernel is built for (its per-node and per-path-level arrays in LDS)
+constexpr int kMaxSims = 100;              // S <= 100 (config (e) uses 100)
+constexpr int kMaxNodes = kMaxSims + 1;
+constexpr int kMaxDepth = 64;
+static inline int check_search_limits(int num_simulations, int max_depth) {
+  const bool ok = num_simulations >= 1 && num_simulations <= kMaxSims && max_depth >= 1 && max_depth <= kMaxDepth;
+  return ok ? MUZ_OK : MUZ_E_UNSUPPORTED;
+}
+
 struct SearchArgs {
   int S, D, max_considered;
   float value_scale, maxvisit_init, gumbel_scale;
@@ -19,6 +28,18 @@ struct SearchArgs {
   int exact_select = 0;   // k_dog_search: every interior selection on the exact path (MUZ_DOG_EXACT_SELECT)
   int games_per_wg = 8;   // k_dog_search one-game-per-wave form: games per workgroup (<= 8; MUZ_DOG_GPW)
 };
+static inline SearchArgs make_search_args(const muz_search_cfg& cfg) {
+  SearchArgs sa;
+  sa.S = cfg.num_simulations;
+  sa.D = cfg.max_depth;
+  sa.max_considered = cfg.max_num_considered;
+  sa.value_scale = cfg.value_scale;
+  sa.maxvisit_init = cfg.maxvisit_init;
+  sa.gumbel_scale = cfg.gumbel_scale;
+  sa.seed = cfg.seed;
+  sa.turn = cfg.turn;
+  return sa;
+}
 
 // host_counts (optional): the self-play ledger's mapped pinned slot; k_repr_conv's first workgroup copies n_dev[0..1]
 // (the turn's searching / active counts, final once the turn head has run) into it

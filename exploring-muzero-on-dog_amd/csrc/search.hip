@@ -8,9 +8,8 @@
 // inter-workgroup traffic (games are independent).  Node scalars (visits, raw value, value) and
 // the current path live in LDS; children arrays and node embeddings live in the workspace (HBM,
 // L2/MALL resident), written lazily when a node is created.
-#include "launch.hpp"
-#include "nn.hpp"
 #include "rng.hpp"
+#include "tree.hpp"
 
 namespace muz {
 
@@ -41,90 +40,15 @@ __device__ unsigned long long g_muz_stamps[8];
 #endif
 constexpr bool kLateHeads = MUZ_LATE_HEADS != 0;
 
-constexpr int kMaxSims = 100;              // S <= 100 (config (e) uses 100)
-constexpr int kMaxNodes = kMaxSims + 1;
-constexpr int kMaxDepth = 64;
 constexpr int kAPad = 32;                  // children arrays padded to 32 actions
-constexpr float kFMin = -3.4028234663852886e38f;   // jnp.finfo(float32).min
-// levels per backup chunk (one per lane); a smaller value only in the test build that exercises the chunked
-// path of max_depth > 32 at ordinary depths (tests/test_gpu_search.py)
+// levels per backup chunk (one per lane; backup_lanes, tree.hpp).  A smaller value (make EXTRA=-DMUZ_BACKUP_CHUNK=4)
+// runs the chunked path of max_depth > 32 at ordinary depths; no committed test builds that variant
 #ifndef MUZ_BACKUP_CHUNK
 #define MUZ_BACKUP_CHUNK kRowLanes
 #endif
 constexpr int kBackupChunk = MUZ_BACKUP_CHUNK;
-static_assert(kBackupChunk >= 1 && kBackupChunk <= kRowLanes, "backup chunk");
 
-struct TreeWs {
-  int32_t* c_index;
-  float* c_prior;
-  float* c_value;
-  int32_t* c_visits;
-  float* c_reward;
-  float* c_disc;
-  float* emb;
-  int N;
-  __device__ __forceinline__ size_t ca(int g, int node, int a) const { return ((size_t)g * N + node) * kAPad + a; }
-  __device__ __forceinline__ AS1 float* e(int g, int node) const { return gpw(emb) + ((size_t)g * N + node) * LAT; }
-  // global-address-space views (see common.hpp: keeps LDS waits independent of global loads)
-  __device__ __forceinline__ AS1 int32_t* index() const { return gpw(c_index); }
-  __device__ __forceinline__ AS1 float* prior() const { return gpw(c_prior); }
-  __device__ __forceinline__ AS1 float* value() const { return gpw(c_value); }
-  __device__ __forceinline__ AS1 int32_t* visits() const { return gpw(c_visits); }
-  __device__ __forceinline__ AS1 float* reward() const { return gpw(c_reward); }
-  __device__ __forceinline__ AS1 float* disc() const { return gpw(c_disc); }
-};
-
-static inline size_t ws_children_bytes(int64_t n, int N) { return (size_t)n * N * kAPad * 4; }
-
-static TreeWs carve_ws(void* ws, int n, int N) {
-  char* p = (char*)ws;
-  const size_t cb = ws_children_bytes(n, N);
-  TreeWs t;
-  t.c_index = (int32_t*)p;
-  p += cb;
-  t.c_prior = (float*)p;
-  p += cb;
-  t.c_value = (float*)p;
-  p += cb;
-  t.c_visits = (int32_t*)p;
-  p += cb;
-  t.c_reward = (float*)p;
-  p += cb;
-  t.c_disc = (float*)p;
-  p += cb;
-  t.emb = (float*)p;
-  t.N = N;
-  return t;
-}
-
-// ---- one game per 32 lanes (half a wave), one action per lane; jnp.argmax tie-break (first index) ----
-__device__ __forceinline__ void row_argmax(float& v, int& i) {
-  // (value, index) pairs under the order "larger value, then smaller index" (jnp.argmax tie-break)
-  auto pick = [](float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  };
-  pick(v, i, dpp<DPP_XOR1>(v), dpp<DPP_XOR1>(i));
-  pick(v, i, dpp<DPP_XOR2>(v), dpp<DPP_XOR2>(i));
-  pick(v, i, dpp<DPP_HALF_MIRROR>(v), dpp<DPP_HALF_MIRROR>(i));
-  pick(v, i, dpp<DPP_MIRROR>(v), dpp<DPP_MIRROR>(i));
-  {
-    const LoHi<float> pv = swap16(v);
-    const LoHi<int> pi = swap16(i);
-    v = pv.lo;
-    i = pi.lo;
-    pick(v, i, pv.hi, pi.hi);
-  }
-  if constexpr (kRowLanes == 64) {
-    const LoHi<float> pv = swap32(v);
-    const LoHi<int> pi = swap32(i);
-    v = pv.lo;
-    i = pi.lo;
-    pick(v, i, pv.hi, pi.hi);
-  }
-}
+using TreeWs = NarrowTree<kAPad>;
 
 // ---- the tree arithmetic, bit for bit like the NumPy restatement (oracle/mctx_gumbel.py) -------------------
 // With identical network outputs on both sides the search's floats then agree exactly (tests/_parity.py):
@@ -143,25 +67,6 @@ __device__ __forceinline__ float row_sum24(float v) {
   v = v + dpp<DPP_XOR1>(v);                     // r0 + r1 | r2 + r3 | ...
   v = v + dpp<DPP_XOR2>(v);                     // (r0 + r1) + (r2 + r3) | (r4 + r5) + (r6 + r7)
   return v + dpp<DPP_HALF_MIRROR>(v);           // lane i <-> 7 - i: the two halves
-}
-__device__ __forceinline__ float exp_cr(float x) { return (float)exp((double)x); }
-
-// seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.
-__device__ __forceinline__ int considered_visit(int m, int S, int idx) {
-  if (m <= 1) return idx;
-  int log2max = 0;
-  while ((1 << log2max) < m) ++log2max;
-  int k = m, v = 0, len = 0;
-  while (len < S) {
-    const int extra = max(1, S / (log2max * k));
-    for (int e = 0; e < extra; ++e) {
-      if (idx < len + k) return v;
-      len += k;
-      ++v;
-    }
-    k = max(2, k / 2);
-  }
-  return v;
 }
 
 // One child edge of the current node, held by lane `a` of the game's 32 lanes (ok = a < A).
@@ -388,55 +293,19 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
         s_val[row][nx] = v;
         s_visits[row][nx] = fresh ? 1 : s_visits[row][nx] + 1;
       }
-      // ---------------- backward (search.py backward) along the recorded path, one level per lane: lane a
-      // holds level base + a (chunks of kRowLanes levels from the top when max_depth > kRowLanes).  Path nodes
-      // are distinct, so every level's parent statistics are read at once; only the discounted leaf value is a
-      // chain, evaluated level by level in the original order (leaf = r + discount * leaf, bit-identical to a
-      // sequential walk) with the level above's value moved down one lane per step.
-      const int d = s_depth[row];
-      float carry = v;      // leaf value entering the chunk from the level above it
-      float carry_v = v;    // new value of the node below the chunk's top level (its tree edge's value)
-      for (int base = ((d - 1) / kBackupChunk) * kBackupChunk; base >= 0; base -= kBackupChunk) {
-        const int l = base + a;
-        const int top = min(d, base + kBackupChunk) - 1 - base;   // highest lane of this row's chunk
-        const bool on = a <= top;
-        int parent = 0, pact = 0, cvis = 0, cnt = 0;
-        float r = 0.f, dsc = 0.f, pval = 0.f;
-        if (on) {
-          parent = p_node[row][l];
-          pact = p_act[row][l];
-          cvis = p_cvis[row][l];
-          r = (l == d - 1) ? rw : p_rew[row][l];
-          dsc = (l == d - 1) ? dc : p_disc[row][l];
-          cnt = s_visits[row][parent];
-          pval = s_val[row][parent];
-        }
-        // highest chunk lane over the wave's two rows (wave-uniform loop bound)
-        const unsigned long long tb = __ballot(a == top);
-        const int k0 = max(tb & 0xFFFFFFFFull ? 31 - __builtin_clz((unsigned)tb) : -1,
-                           tb >> 32 ? 31 - __builtin_clz((unsigned)(tb >> 32)) : -1);
-        float leaf = 0.f;
-        for (int k = k0; k >= 0; --k) {
-          const float up = dpp<DPP_WAVE_SHL1>(leaf);   // lane a + 1's value
-          if (a == k && on) leaf = r + dsc * (a == top ? carry : up);
-        }
-        const float pv = (pval * (float)cnt + leaf) / ((float)cnt + 1.0f);
-        const float pv_up = dpp<DPP_WAVE_SHL1>(pv);
-        const float child_v = (a == top) ? carry_v : pv_up;
-        if (on) {
-          if (l > 0) {
-            const size_t ei = T.ca(g, parent, pact);
-            tree_st(T.value() + ei, child_v);
-            tree_st(T.visits() + ei, cvis + 1);
-          } else {
-            s_rootv[row] = child_v;
-          }
-          s_val[row][parent] = pv;
-          s_visits[row][parent] = cnt + 1;
-        }
-        carry = __shfl(leaf, 0, kRowLanes);
-        carry_v = __shfl(pv, 0, kRowLanes);
-      }
+      // ---------------- backward (search.py backward) along the recorded path: an interior edge's new value and
+      // visit count go to the tree, the root edge's value (level 0: registers) to s_rootv
+      const PathRow path{p_node[row], p_act[row], p_cvis[row], p_rew[row], p_disc[row], s_visits[row], s_val[row]};
+      backup_lanes<kBackupChunk>(path, a, s_depth[row], v, rw, dc,
+                                 [&](int l, int parent, int pact, int cvis, float, float, float child_v) {
+                                   if (l > 0) {
+                                     const size_t ei = T.ca(g, parent, pact);
+                                     tree_st(T.value() + ei, child_v);
+                                     tree_st(T.visits() + ei, cvis + 1);
+                                   } else {
+                                     s_rootv[row] = child_v;
+                                   }
+                                 });
       // the root edge of this path (level 0): its lane takes the value lane 0 just backed up
       // (same wave: LDS operations of one wave complete in order)
       __builtin_amdgcn_wave_barrier();
@@ -484,16 +353,13 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   }
 }
 
-int64_t search_workspace_bytes(int n, int S) {
-  const int N = S + 1;
-  return (int64_t)ws_children_bytes(n, N) * 6 + (int64_t)n * N * LAT * 4;
-}
+int64_t search_workspace_bytes(int n, int S) { return (int64_t)TreeWs::bytes(n, S + 1); }
 
 int launch_gumbel_search(const muz_net_w& w, const SearchArgs& sa, const float* root_logits, const float* root_value,
                          const float* root_emb, const uint32_t* legal, const float* gumbel, const int32_t* game_id,
                          int n, const int* n_dev, void* workspace, int32_t* action, float* weights, float* value,
                          hipStream_t s) {
-  TreeWs T = carve_ws(workspace, n, sa.S + 1);
+  const TreeWs T = TreeWs::carve(workspace, n, sa.S + 1);
   k_gumbel_search<<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal,
                                                                gumbel, game_id, n, n_dev, T, action, weights, value);
   return muz_last_launch_error();
@@ -516,23 +382,13 @@ int muz_gumbel_search(const muz_net_w* w, const muz_search_cfg* cfg, const float
                       float* action_weights, float* root_value_out, void* stream) {
   if (!w || !cfg) return MUZ_E_INVALID;
   if (w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
-  if (cfg->num_simulations < 1 || cfg->num_simulations > kMaxSims) return MUZ_E_UNSUPPORTED;
-  if (cfg->max_depth < 1 || cfg->max_depth > kMaxDepth) return MUZ_E_UNSUPPORTED;
+  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
   if (cfg->max_num_considered < 1) return MUZ_E_UNSUPPORTED;
   MUZ_HOST_CHECK(n >= 0 && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
                  action_weights && root_value_out);
   MUZ_HOST_CHECK(workspace_bytes >= search_workspace_bytes(n, cfg->num_simulations));
   if (n == 0) return MUZ_OK;
-  SearchArgs sa;
-  sa.S = cfg->num_simulations;
-  sa.D = cfg->max_depth;
-  sa.max_considered = cfg->max_num_considered;
-  sa.value_scale = cfg->value_scale;
-  sa.maxvisit_init = cfg->maxvisit_init;
-  sa.gumbel_scale = cfg->gumbel_scale;
-  sa.seed = cfg->seed;
-  sa.turn = cfg->turn;
-  return launch_gumbel_search(*w, sa, root_logits, root_value, root_embedding, legal_bits, gumbel, game_id, n, nullptr,
+  return launch_gumbel_search(*w, make_search_args(*cfg), root_logits, root_value, root_embedding, legal_bits, gumbel, game_id, n, nullptr,
                               workspace, action, action_weights, root_value_out, (hipStream_t)stream);
 }
 

@@ -9,10 +9,9 @@
 #include "compact.hpp"
 #include "host_consts.hpp"
 #include "launch.hpp"
-#include "turn_ledger.hpp"
 #include "rng.hpp"
-
-#include <algorithm>
+#include "selfplay_host.hpp"
+#include "turn_ledger.hpp"
 
 namespace muz {
 
@@ -169,8 +168,9 @@ __global__ void k_cs_init(DetConsts c, muz_classic_soa st, int32_t* lane_game, i
   cls_reset_lane(c, st, l);
 }
 
-// Streaming refill (see selfplay.hip k_ss_refill): lanes whose game ended take the next game numbers in
-// lane order and are reset; lanes left without a game go idle.
+// Streaming refill (one workgroup, deterministic): every lane whose game ended (done, or its record is full) takes
+// the next unplayed game number in lane order and is reset; lanes left without a game go idle (-1).  next[0] = next
+// unplayed game number.
 __global__ __launch_bounds__(kScanThreads) void k_cs_refill(DetConsts c, muz_classic_soa st, int32_t* lane_game,
                                                             const int32_t* idx, int T, int32_t* next, int num_games,
                                                             int W) {
@@ -208,61 +208,9 @@ __global__ __launch_bounds__(kScanThreads) void k_cs_refill(DetConsts c, muz_cla
   if (t == kScanThreads - 1) next[0] = min(num_games, base + part[t]);
 }
 
-struct CsWs {
-  void* tree;
-  float* conv;
-  float* obs;
-  uint32_t* legal;
-  uint32_t* legal_c;
-  int32_t* flag;
-  int32_t* slot;
-  int32_t* list;
-  float* root_logits;
-  float* root_value;
-  float* root_emb;
-  int32_t* action;
-  float* weights;
-  float* value;
-  int32_t* counts;
-  int32_t* lane_game;
-  int32_t* next_game;
-};
-
-static inline size_t cal256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-static size_t cs_carve(char* base, int n, int C, int S, CsWs* w) {
-  const size_t n16 = (size_t)((n + 15) / 16 * 16);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    char* p = base ? base + off : nullptr;
-    off += cal256(bytes);
-    return p;
-  };
-  CsWs t;
-  t.tree = take((size_t)stochastic_workspace_bytes(n, S));
-  t.conv = (float*)take(n16 * kConvRowFloats * 4);
-  t.obs = (float*)take(n16 * C * kCells * 4);
-  t.legal = (uint32_t*)take((size_t)n * 4);
-  t.legal_c = (uint32_t*)take((size_t)n * 4);
-  t.flag = (int32_t*)take((size_t)n * 4);
-  t.slot = (int32_t*)take((size_t)n * 4);
-  t.list = (int32_t*)take((size_t)n * 4);
-  t.root_logits = (float*)take(n16 * MUZ_CLASSIC_ACTIONS * 4);
-  t.root_value = (float*)take(n16 * 4);
-  t.root_emb = (float*)take(n16 * 256 * 4);
-  t.action = (int32_t*)take(n16 * 4);
-  t.weights = (float*)take(n16 * MUZ_CLASSIC_ACTIONS * 4);
-  t.value = (float*)take(n16 * 4);
-  t.counts = (int32_t*)take(64);
-  t.lane_game = (int32_t*)take((size_t)n * 4);
-  t.next_game = (int32_t*)take(64);
-  if (w) *w = t;
-  return off;
-}
-
 // Turn loop shared by the batch and the streaming driver (see selfplay.hip sp_turns).
 static int cs_turns(const DetConsts& c, const muz_classic_net_w* w, const muz_stoch_cfg* cfg, muz_classic_soa st,
-                    muz_traj tr, muz_traj_chance ch, int n, const CsWs& ws, const int32_t* lane_game, int num_games,
+                    muz_traj tr, muz_traj_chance ch, int n, const SpWs& ws, const int32_t* lane_game, int num_games,
                     int max_turns, muz_sp_stats* stats, hipStream_t s) {
   const int T = tr.max_steps;
   int rc = MUZ_OK;
@@ -302,6 +250,27 @@ static int cs_turns(const DetConsts& c, const muz_classic_net_w* w, const muz_st
 }
 
 
+static size_t cs_carve(char* base, int n, int C, int S, SpWs* ws) {
+  return sp_carve(base, n, C, MUZ_CLASSIC_ACTIONS, (size_t)stochastic_workspace_bytes(n, S), ws);
+}
+
+// The checks of both entry points (`lanes` games at a time out of num_games), then the carve
+static int cs_setup(const muz_rules* rules, const muz_classic_net_w* w, const muz_stoch_cfg* cfg,
+                    const muz_classic_soa& st, const muz_traj& tr, const muz_traj_chance& ch, int lanes, int num_games,
+                    void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, DetConsts* c, SpWs* ws) {
+  int rc = make_det_consts(rules, c);
+  if (rc) return rc;
+  if (!cfg) return MUZ_E_INVALID;
+  if ((rc = check_classic_net(w))) return rc;
+  if (w->obs_channels != 2 * c->P + 3) return MUZ_E_UNSUPPORTED;
+  MUZ_HOST_CHECK(sp_args_ok(lanes, num_games, st.stride, workspace, tr, false) && ch.dice && ch.dice_dist);
+  if ((rc = check_search_limits(cfg->num_simulations, cfg->max_depth))) return rc;
+  if (stats) *stats = muz_sp_stats{};
+  MUZ_HOST_CHECK(workspace_bytes >= (int64_t)cs_carve(nullptr, lanes, w->obs_channels, cfg->num_simulations, nullptr));
+  cs_carve((char*)workspace, lanes, w->obs_channels, cfg->num_simulations, ws);
+  return MUZ_OK;
+}
+
 }  // namespace muz
 
 using namespace muz;
@@ -317,84 +286,31 @@ int muz_classic_selfplay(const muz_rules* rules, const muz_classic_net_w* w, con
                          muz_classic_soa st, muz_traj tr, muz_traj_chance ch, int32_t n, void* workspace,
                          int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
   DetConsts c;
-  int rc = make_det_consts(rules, &c);
-  if (rc) return rc;
-  if (!cfg) return MUZ_E_INVALID;
-  if ((rc = check_classic_net(w))) return rc;
-  if (w->obs_channels != 2 * c.P + 3) return MUZ_E_UNSUPPORTED;
-  MUZ_HOST_CHECK(n >= 0 && st.stride >= n && workspace && tr.max_steps > 0 && tr.obs && tr.act && tr.rew &&
-                 tr.val && tr.pol && tr.mask && tr.player && tr.team && tr.discount && tr.idx && ch.dice &&
-                 ch.dice_dist);
-  if (cfg->num_simulations < 1 || cfg->num_simulations > 100 || cfg->max_depth < 1 || cfg->max_depth > 64)
-    return MUZ_E_UNSUPPORTED;
-  if (stats) *stats = muz_sp_stats{};
-  MUZ_HOST_CHECK(workspace_bytes >= (int64_t)cs_carve(nullptr, n, w->obs_channels, cfg->num_simulations, nullptr));
-  if (n == 0) return MUZ_OK;
+  SpWs ws;
+  int rc = cs_setup(rules, w, cfg, st, tr, ch, n, n, workspace, workspace_bytes, stats, &c, &ws);
+  if (rc || n == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int C = w->obs_channels;
-  const int T = tr.max_steps;
-  CsWs ws;
-  cs_carve((char*)workspace, n, C, cfg->num_simulations, &ws);
-
   k_cs_reset<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
-  const size_t nt = (size_t)n * T;
-  MUZ_HIP_RET(hipMemsetAsync(tr.obs, 0, nt * C * kCells, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.act, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.rew, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.val, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.pol, 0, nt * MUZ_CLASSIC_ACTIONS * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.mask, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.player, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.team, 0xFF, nt * 4, s));   // jnp.full(..., -1)
-  MUZ_HIP_RET(hipMemsetAsync(tr.discount, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.idx, 0, (size_t)n * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(ch.dice, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(ch.dice_dist, 0, nt * 6 * 4, s));
-
-  return cs_turns(c, w, cfg, st, tr, ch, n, ws, nullptr, n, T, stats, s);
+  if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_CLASSIC_ACTIONS, s))) return rc;
+  if ((rc = traj_clear(ch, n, tr.max_steps, s))) return rc;
+  return cs_turns(c, w, cfg, st, tr, ch, n, ws, nullptr, n, tr.max_steps, stats, s);
 }
 
 int muz_classic_selfplay_stream(const muz_rules* rules, const muz_classic_net_w* w, const muz_stoch_cfg* cfg,
                                 muz_classic_soa st, muz_traj tr, muz_traj_chance ch, int32_t num_games, int32_t lanes,
                                 void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
   DetConsts c;
-  int rc = make_det_consts(rules, &c);
-  if (rc) return rc;
-  if (!cfg) return MUZ_E_INVALID;
-  if ((rc = check_classic_net(w))) return rc;
-  if (w->obs_channels != 2 * c.P + 3) return MUZ_E_UNSUPPORTED;
+  SpWs ws;
   const int n = lanes;
-  MUZ_HOST_CHECK(n >= 0 && num_games >= 0 && st.stride >= n && workspace && tr.max_steps > 0 && tr.obs && tr.act &&
-                 tr.rew && tr.val && tr.pol && tr.mask && tr.player && tr.team && tr.discount && tr.idx && ch.dice &&
-                 ch.dice_dist);
-  if (cfg->num_simulations < 1 || cfg->num_simulations > 100 || cfg->max_depth < 1 || cfg->max_depth > 64)
-    return MUZ_E_UNSUPPORTED;
-  if (stats) *stats = muz_sp_stats{};
-  MUZ_HOST_CHECK(workspace_bytes >= (int64_t)cs_carve(nullptr, n, w->obs_channels, cfg->num_simulations, nullptr));
-  if (n == 0 || num_games == 0) return MUZ_OK;
+  int rc = cs_setup(rules, w, cfg, st, tr, ch, n, num_games, workspace, workspace_bytes, stats, &c, &ws);
+  if (rc || n == 0 || num_games == 0) return rc;
   hipStream_t s = (hipStream_t)stream;
-  const int C = w->obs_channels;
-  const int T = tr.max_steps;
-  CsWs ws;
-  cs_carve((char*)workspace, n, C, cfg->num_simulations, &ws);
-  const size_t nt = (size_t)num_games * T;
-  MUZ_HIP_RET(hipMemsetAsync(tr.obs, 0, nt * C * kCells, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.act, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.rew, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.val, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.pol, 0, nt * MUZ_CLASSIC_ACTIONS * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.mask, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.player, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.team, 0xFF, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.discount, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(tr.idx, 0, (size_t)num_games * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(ch.dice, 0, nt * 4, s));
-  MUZ_HIP_RET(hipMemsetAsync(ch.dice_dist, 0, nt * 6 * 4, s));
+  if ((rc = traj_clear(tr, num_games, w->obs_channels, MUZ_CLASSIC_ACTIONS, s))) return rc;
+  if ((rc = traj_clear(ch, num_games, tr.max_steps, s))) return rc;
   k_cs_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
   MUZ_HIP_RET(hipGetLastError());
-  const long long gens = ((long long)num_games + n - 1) / n;
-  const int max_turns = (int)std::min<long long>(gens * T + 1, 1 << 30);
-  return cs_turns(c, w, cfg, st, tr, ch, n, ws, ws.lane_game, num_games, max_turns, stats, s);
+  return cs_turns(c, w, cfg, st, tr, ch, n, ws, ws.lane_game, num_games, stream_max_turns(num_games, n, tr.max_steps),
+                  stats, s);
 }
 
 }  // extern "C"

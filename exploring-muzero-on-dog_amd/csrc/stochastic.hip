@@ -13,100 +13,41 @@
 //   backup  -- as in mctx search.backward.
 // mctx evaluates both recurrent functions for every expansion and keeps one per lane; the other output is
 // never read, so evaluating only the needed one gives identical trees.
-#include "launch.hpp"
 #include "rng.hpp"
 #include "sdyn.hpp"
+#include "tree.hpp"
 
 namespace muz {
 
-constexpr int kSMaxSims = 100;
-constexpr int kSMaxNodes = kSMaxSims + 1;
-constexpr int kSMaxDepth = 64;
 constexpr int kSA = 16;                 // child slots per node (A' = 10 used)
 constexpr int kCls = 4, kChance = MUZ_CHANCE_OUTCOMES, kAp = kCls + kChance;
-constexpr float kSFMin = -3.4028234663852886e38f;
 
 #ifdef MUZ_BRANCH_STATS
 __device__ unsigned long long g_branch_hist[(kRows + 1) * (kRows + 1)];
 #endif
 
-struct STree {
-  int32_t* c_index;
-  float* c_prior;
-  float* c_value;
-  int32_t* c_visits;
-  float* c_reward;
-  float* c_disc;
-  float* emb;    // [n][N][256]  decision: state embedding, chance: afterstate
-  float* info;   // [n][N][2]    chance nodes: (reward, discount) of the decision step (afterstate_with_info)
-  int N;
-  __device__ __forceinline__ size_t ca(int g, int node, int a) const { return ((size_t)g * N + node) * kSA + a; }
-  __device__ __forceinline__ AS1 float* e(int g, int node) const { return gpw(emb) + ((size_t)g * N + node) * LAT; }
-  __device__ __forceinline__ AS1 float* inf(int g, int node) const { return gpw(info) + ((size_t)g * N + node) * 2; }
-  __device__ __forceinline__ AS1 int32_t* index() const { return gpw(c_index); }
-  __device__ __forceinline__ AS1 float* prior() const { return gpw(c_prior); }
-  __device__ __forceinline__ AS1 float* value() const { return gpw(c_value); }
-  __device__ __forceinline__ AS1 int32_t* visits() const { return gpw(c_visits); }
-  __device__ __forceinline__ AS1 float* reward() const { return gpw(c_reward); }
-  __device__ __forceinline__ AS1 float* disc() const { return gpw(c_disc); }
+// The narrow tree (emb: a decision node's state embedding, a chance node's afterstate) and, the workspace's last
+// piece, info [n][N][2]: a chance node's (reward, discount) of the decision step (afterstate_with_info)
+struct STreeArrays : TreeArrays {
+  float* info;
 };
+struct STree : NarrowTree<kSA, STreeArrays> {
+  using Narrow = NarrowTree<kSA, STreeArrays>;
+  __device__ __forceinline__ AS1 float* inf(int g, int node) const { return gpw(info) + ((size_t)g * N + node) * 2; }
 
-static inline size_t stree_child_bytes(int64_t n, int N) { return (size_t)n * N * kSA * 4; }
-
-static STree carve_stree(void* ws, int n, int N) {
-  char* p = (char*)ws;
-  const size_t cb = stree_child_bytes(n, N);
-  STree t;
-  t.c_index = (int32_t*)p;
-  p += cb;
-  t.c_prior = (float*)p;
-  p += cb;
-  t.c_value = (float*)p;
-  p += cb;
-  t.c_visits = (int32_t*)p;
-  p += cb;
-  t.c_reward = (float*)p;
-  p += cb;
-  t.c_disc = (float*)p;
-  p += cb;
-  t.emb = (float*)p;
-  p += (size_t)n * N * LAT * 4;
-  t.info = (float*)p;
-  t.N = N;
-  return t;
-}
+  static size_t bytes(int64_t n, int N) { return Narrow::bytes(n, N) + (size_t)n * N * 2 * 4; }
+  static STree carve(void* ws, int n, int N) {
+    STree t;
+    static_cast<Narrow&>(t) = Narrow::carve(ws, n, N);
+    t.info = (float*)((char*)ws + Narrow::bytes(n, N));
+    return t;
+  }
+};
 
 struct SKid {
   float prior, value, reward, disc;
   int visits, index;
 };
-
-__device__ __forceinline__ void srow_argmax(float& v, int& i) {
-  auto pick = [](float& v, int& i, float ov, int oi) {
-    if (ov > v || (ov == v && oi < i)) {
-      v = ov;
-      i = oi;
-    }
-  };
-  pick(v, i, dpp<DPP_XOR1>(v), dpp<DPP_XOR1>(i));
-  pick(v, i, dpp<DPP_XOR2>(v), dpp<DPP_XOR2>(i));
-  pick(v, i, dpp<DPP_HALF_MIRROR>(v), dpp<DPP_HALF_MIRROR>(i));
-  pick(v, i, dpp<DPP_MIRROR>(v), dpp<DPP_MIRROR>(i));
-  {
-    const LoHi<float> pv = swap16(v);
-    const LoHi<int> pi = swap16(i);
-    v = pv.lo;
-    i = pi.lo;
-    pick(v, i, pv.hi, pi.hi);
-  }
-  if constexpr (kRowLanes == 64) {
-    const LoHi<float> pv = swap32(v);
-    const LoHi<int> pi = swap32(i);
-    v = pv.lo;
-    i = pi.lo;
-    pick(v, i, pv.hi, pi.hi);
-  }
-}
 
 // ---- FiLM tables (muz_classic_net_prepare) -------------------------------------------------------
 // tab[o][0:512] = film(relu(embed(one_hot(o)))) for o < nrow, row nrow = zero one-hot.
@@ -194,15 +135,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
   // tree arithmetic exactly as written (no fused multiply-add), like the NumPy restatement of mctx
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
-  __shared__ int s_visits[kRows][kSMaxNodes];
-  __shared__ float s_raw[kRows][kSMaxNodes];
-  __shared__ float s_val[kRows][kSMaxNodes];
-  __shared__ uint8_t s_dec[kRows][kSMaxNodes];
-  __shared__ int p_node[kRows][kSMaxDepth];
-  __shared__ int p_act[kRows][kSMaxDepth];
-  __shared__ int p_cvis[kRows][kSMaxDepth];
-  __shared__ float p_rew[kRows][kSMaxDepth];
-  __shared__ float p_disc[kRows][kSMaxDepth];
+  __shared__ int s_visits[kRows][kMaxNodes];
+  __shared__ float s_raw[kRows][kMaxNodes];
+  __shared__ float s_val[kRows][kMaxNodes];
+  __shared__ uint8_t s_dec[kRows][kMaxNodes];
+  __shared__ int p_node[kRows][kMaxDepth];
+  __shared__ int p_act[kRows][kMaxDepth];
+  __shared__ int p_cvis[kRows][kMaxDepth];
+  __shared__ float p_rew[kRows][kMaxDepth];
+  __shared__ float p_disc[kRows][kMaxDepth];
   __shared__ int s_act[kRows], s_parent[kRows], s_next[kRows], s_depth[kRows], s_decp[kRows];
   __shared__ float s_newr[kRows], s_newd[kRows], s_rootv[kRows];
   __shared__ float s_cl[kRows][kChance];
@@ -247,7 +188,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
     float lg = act_lane ? logf(fmaxf(noisy, kTinyF)) : -INFINITY;
     lg = lg - row_max(lg);
     const bool inv = !act_lane || ((lb >> a) & 1u) == 0u;
-    rk.prior = act_lane ? (inv ? kSFMin : lg) : -INFINITY;
+    rk.prior = act_lane ? (inv ? kFMin : lg) : -INFINITY;
     AS1 float* e0 = T.e(g, 0);
     for (int c = a; c < LAT; c += kRowLanes) e0[c] = root_emb[(size_t)g * LAT + c];
     if (a == 0) {
@@ -314,7 +255,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
           sc = cl ? pc / (float)(k.visits + 1) : -INFINITY;
         }
         int bi = a;
-        srow_argmax(sc, bi);
+        row_argmax(sc, bi);
         const int child = __shfl(k.index, bi, kRowLanes);
         if (a == bi) {
           p_node[row][depth] = node;
@@ -485,7 +426,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
     const float gmb = act_lane ? (gumbel_in ? gumbel_in[(size_t)g * A + a] : gumbel_noise(sa.seed ^ 0xC2B2AE3D27D4EB4Full, gid, gturn, a)) : 0.f;
     float sc = act_lane ? lw + gmb : -INFINITY;
     int bi = a;
-    srow_argmax(sc, bi);
+    row_argmax(sc, bi);
     if (act_lane) out_weights[(size_t)g * A + a] = w;
     if (a == 0) {
       out_action[g] = bi;
@@ -494,10 +435,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
   }
 }
 
-int64_t stochastic_workspace_bytes(int n, int S) {
-  const int N = S + 1;
-  return (int64_t)(6 * stree_child_bytes(n, N) + (size_t)n * N * LAT * 4 + (size_t)n * N * 2 * 4);
-}
+int64_t stochastic_workspace_bytes(int n, int S) { return (int64_t)STree::bytes(n, S + 1); }
 
 SArgs make_sargs(const muz_stoch_cfg& cfg, int A) {
   SArgs sa;
@@ -518,7 +456,7 @@ int launch_stochastic_search(const muz_classic_net_w& w, const SArgs& sa, const 
                              const float* root_value, const float* root_emb, const uint32_t* legal,
                              const float* dirichlet, const float* gumbel, const int32_t* game_id, int n, const int* n_dev,
                              void* workspace, int32_t* action, float* weights, float* value, hipStream_t s) {
-  const STree T = carve_stree(workspace, n, sa.S + 1);
+  const STree T = STree::carve(workspace, n, sa.S + 1);
   k_stochastic_search<<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal,
                                                                    dirichlet, gumbel, game_id, n, n_dev, T, action,
                                                                    weights, value);
@@ -611,8 +549,7 @@ int muz_stochastic_search(const muz_classic_net_w* w, const muz_stoch_cfg* cfg, 
   if (rc) return rc;
   MUZ_HOST_CHECK(cfg && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
                  action_weights && root_value_out && n >= 0);
-  if (cfg->num_simulations < 1 || cfg->num_simulations > kSMaxSims) return MUZ_E_UNSUPPORTED;
-  if (cfg->max_depth < 1 || cfg->max_depth > kSMaxDepth) return MUZ_E_UNSUPPORTED;
+  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
   MUZ_HOST_CHECK(workspace_bytes >= stochastic_workspace_bytes(n, cfg->num_simulations));
   if (n == 0) return MUZ_OK;
   return launch_stochastic_search(*w, make_sargs(*cfg, w->num_actions), root_logits, root_value, root_embedding,

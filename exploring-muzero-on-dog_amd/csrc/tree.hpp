@@ -1,0 +1,174 @@
+// The tree machinery the persistent search kernels share (k_gumbel_search, k_stochastic_search, k_dog_search): one
+// game per kRowLanes lanes, node scalars and the current path in LDS, children arrays and node embeddings in the
+// workspace.  The limits (kMaxSims, kMaxNodes, kMaxDepth) sit beside SearchArgs in launch.hpp, where the host entry
+// points read them too.
+#pragma once
+#include "launch.hpp"
+#include "nn.hpp"
+
+namespace muz {
+inline namespace MUZ_NN_NS {   // (built on tid(): see the note at the top of nn.hpp)
+
+constexpr float kFMin = -3.4028234663852886e38f;   // jnp.finfo(float32).min
+
+// (value, index) argmax across the row's lanes under the order "larger value, then smaller index" (jnp.argmax
+// tie-break: the first index)
+__device__ __forceinline__ void row_argmax(float& v, int& i) {
+  auto pick = [](float& v, int& i, float ov, int oi) {
+    if (ov > v || (ov == v && oi < i)) {
+      v = ov;
+      i = oi;
+    }
+  };
+  pick(v, i, dpp<DPP_XOR1>(v), dpp<DPP_XOR1>(i));
+  pick(v, i, dpp<DPP_XOR2>(v), dpp<DPP_XOR2>(i));
+  pick(v, i, dpp<DPP_HALF_MIRROR>(v), dpp<DPP_HALF_MIRROR>(i));
+  pick(v, i, dpp<DPP_MIRROR>(v), dpp<DPP_MIRROR>(i));
+  {
+    const LoHi<float> pv = swap16(v);
+    const LoHi<int> pi = swap16(i);
+    v = pv.lo;
+    i = pi.lo;
+    pick(v, i, pv.hi, pi.hi);
+  }
+  if constexpr (kRowLanes == 64) {
+    const LoHi<float> pv = swap32(v);
+    const LoHi<int> pi = swap32(i);
+    v = pv.lo;
+    i = pi.lo;
+    pick(v, i, pv.hi, pi.hi);
+  }
+}
+
+// exp correctly rounded: evaluated in float64 and rounded once, like oracle/mctx_gumbel.py exp_cr (numpy's float32
+// exp and the device's expf are each ~1 ulp off in different places)
+// (A/B, profiles/r4k_dog_ab.log: a float __expf in its place -- wrong rounding -- was 22-27 % faster per DOG search)
+__device__ __forceinline__ float exp_cr(float x) { return (float)exp((double)x); }
+
+// seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.
+__device__ __forceinline__ int considered_visit(int m, int S, int idx) {
+  if (m <= 1) return idx;
+  int log2max = 0;
+  while ((1 << log2max) < m) ++log2max;
+  int k = m, v = 0, len = 0;
+  while (len < S) {
+    const int extra = max(1, S / (log2max * k));
+    for (int e = 0; e < extra; ++e) {
+      if (idx < len + k) return v;
+      len += k;
+      ++v;
+    }
+    k = max(2, k / 2);
+  }
+  return v;
+}
+
+// A narrow tree's workspace: six children arrays [n][N][APAD] (a node's A <= APAD children padded to APAD), then the
+// node embeddings [n][N][256].  Arrays: TreeArrays, or a struct derived from it for a kernel that keeps further
+// per-node arrays after these (the kernel argument's layout is the arrays, then N).
+struct TreeArrays {
+  int32_t* c_index;
+  float* c_prior;
+  float* c_value;
+  int32_t* c_visits;
+  float* c_reward;
+  float* c_disc;
+  float* emb;
+};
+template <int APAD, class Arrays = TreeArrays>
+struct NarrowTree : Arrays {
+  int N;
+  __device__ __forceinline__ size_t ca(int g, int node, int a) const { return ((size_t)g * N + node) * APAD + a; }
+  __device__ __forceinline__ AS1 float* e(int g, int node) const {
+    return gpw(this->emb) + ((size_t)g * N + node) * LAT;
+  }
+  // global-address-space views (see common.hpp: keeps LDS waits independent of global loads)
+  __device__ __forceinline__ AS1 int32_t* index() const { return gpw(this->c_index); }
+  __device__ __forceinline__ AS1 float* prior() const { return gpw(this->c_prior); }
+  __device__ __forceinline__ AS1 float* value() const { return gpw(this->c_value); }
+  __device__ __forceinline__ AS1 int32_t* visits() const { return gpw(this->c_visits); }
+  __device__ __forceinline__ AS1 float* reward() const { return gpw(this->c_reward); }
+  __device__ __forceinline__ AS1 float* disc() const { return gpw(this->c_disc); }
+
+  static size_t child_bytes(int64_t n, int N) { return (size_t)n * N * APAD * 4; }
+  static size_t bytes(int64_t n, int N) { return 6 * child_bytes(n, N) + (size_t)n * N * LAT * 4; }
+  static NarrowTree carve(void* ws, int n, int N) {
+    char* p = (char*)ws;
+    const size_t cb = child_bytes(n, N);
+    NarrowTree t;
+    t.c_index = (int32_t*)p;
+    t.c_prior = (float*)(p + cb);
+    t.c_value = (float*)(p + 2 * cb);
+    t.c_visits = (int32_t*)(p + 3 * cb);
+    t.c_reward = (float*)(p + 4 * cb);
+    t.c_disc = (float*)(p + 5 * cb);
+    t.emb = (float*)(p + 6 * cb);
+    t.N = N;
+    return t;
+  }
+};
+
+// One row's recorded path (an entry per level: node, chosen child, the child's visit-count word, its reward and
+// discount) and its node statistics, all in LDS.
+struct PathRow {
+  const int* node;
+  const int* act;
+  const int* cvis;
+  const float* rew;
+  const float* disc;
+  int* visits;
+  float* val;
+};
+
+// search.py backward along the recorded path of depth d, one level per lane: lane a of the row's lanes holds level
+// base + a (chunks of CHUNK levels from the top when d > CHUNK).  Path nodes are distinct, so every level's parent
+// statistics are read at once; only the discounted leaf value is a chain, evaluated level by level in the original
+// order (leaf = r + discount * leaf, bit-identical to a sequential walk) with the level above's value moved down one
+// lane per step.  v: the new leaf's value; rw, dc: the reward and discount of the path's last edge (the expansion's).
+// The parents' values and visit counts are updated here; edge(l, parent, pact, the level's cvis word, r, dsc,
+// child_v) is called once per level for what the kernel keeps per edge (child_v: the new value of the edge's child).
+template <int CHUNK, class Edge>
+__device__ __forceinline__ void backup_lanes(const PathRow& p, int a, int d, float v, float rw, float dc, Edge edge) {
+#pragma clang fp contract(off)
+  static_assert(CHUNK >= 1 && CHUNK <= kRowLanes && CHUNK <= 32, "one level per lane (the ballot's 32-lane halves)");
+  float carry = v;      // leaf value entering the chunk from the level above it
+  float carry_v = v;    // new value of the node below the chunk's top level (its tree edge's value)
+  for (int base = ((d - 1) / CHUNK) * CHUNK; base >= 0; base -= CHUNK) {
+    const int l = base + a;
+    const int top = min(d, base + CHUNK) - 1 - base;   // highest lane of this row's chunk
+    const bool on = a <= top;
+    int parent = 0, pact = 0, cvis = 0, cnt = 0;
+    float r = 0.f, dsc = 0.f, pval = 0.f;
+    if (on) {
+      parent = p.node[l];
+      pact = p.act[l];
+      cvis = p.cvis[l];
+      r = (l == d - 1) ? rw : p.rew[l];
+      dsc = (l == d - 1) ? dc : p.disc[l];
+      cnt = p.visits[parent];
+      pval = p.val[parent];
+    }
+    // highest chunk lane over the wave's two rows (wave-uniform loop bound)
+    const unsigned long long tb = __ballot(a == top);
+    const int k0 = max(tb & 0xFFFFFFFFull ? 31 - __builtin_clz((unsigned)tb) : -1,
+                       tb >> 32 ? 31 - __builtin_clz((unsigned)(tb >> 32)) : -1);
+    float leaf = 0.f;
+    for (int k = k0; k >= 0; --k) {
+      const float up = dpp<DPP_WAVE_SHL1>(leaf);   // lane a + 1's value
+      if (a == k && on) leaf = r + dsc * (a == top ? carry : up);
+    }
+    const float pv = (pval * (float)cnt + leaf) / ((float)cnt + 1.0f);
+    const float pv_up = dpp<DPP_WAVE_SHL1>(pv);
+    const float child_v = (a == top) ? carry_v : pv_up;
+    if (on) {
+      edge(l, parent, pact, cvis, r, dsc, child_v);
+      p.val[parent] = pv;
+      p.visits[parent] = cnt + 1;
+    }
+    carry = __shfl(leaf, 0, kRowLanes);
+    carry_v = __shfl(pv, 0, kRowLanes);
+  }
+}
+
+}  // namespace MUZ_NN_NS
+}  // namespace muz

@@ -69,7 +69,7 @@ def test_ctypes_struct_layout_matches_header():
 
 
 def considered_visit_closed_form(m, S, idx):
-    """Python twin of csrc/search.hip:considered_visit (table-free seq-halving lookup)."""
+    """Python twin of csrc/tree.hpp:considered_visit (table-free seq-halving lookup)."""
     if m <= 1:
         return idx
     log2max = 0
