@@ -8,6 +8,11 @@
 // trip inside a turn: batch sizes live on the device (`counts`), surplus workgroups exit early.
 // The host checks the active-game count two turns late (pinned memory + events), so the GPU queue
 // never drains; the at most two trailing turns it launches find no active game and record nothing.
+// The streaming driver's turn head also plays no-move turns where it finds them (fast-forward, k_sp_head), so a
+// game without a move does not sit out a whole launched turn; MUZ_SP_FASTFORWARD=0 turns that off.
+#include <algorithm>
+#include <cstdlib>
+
 #include "detmadn.hpp"
 #include "host_consts.hpp"
 #include "launch.hpp"
@@ -122,6 +127,10 @@ __global__ void k_det_reset_sp(DetConsts c, muz_detmadn_soa st, int n) {
 //    (-1).  next[0] counts the numbers handed out;
 //  * flags: the legal mask of every lane's game (det_legal_g, one ballot per 32 actions) and 1 = searches (a legal
 //    move), 2 = no move (no_step), 0 = idle;
+//  * fast-forward (streaming driver, kSpFfCap below): a game flagged 2 plays its no_step turn at once on its LDS
+//    rows (sp_apply_game with f == 2) and is flagged again for the next player, until it has a move, its record is
+//    full (idle this turn, refilled by the next head) or the cap; flag, mask, slot and counts below are those of
+//    the state after it, and idx is final in global memory before the search reads it as key_turn;
 //  * compaction: slot sl of the searching games plays lane list[sl]; counts = (searching, active);
 //  * encode: the observation of every searching game at its slot as fp32 for root inference + its int8 trajectory
 //    record.  The game's lanes stage the encode in LDS (det_enc_stage: rel[56] + constant channels) and write both
@@ -141,6 +150,13 @@ __global__ void k_det_reset_sp(DetConsts c, muz_detmadn_soa st, int n) {
 // 32 games per workgroup (128 workgroups at 4096 lanes): the same-address atomics serialise, so fewer, larger
 // workgroups take fewer of them.
 constexpr int kHeadBlock = 1024;
+// Fast-forward (streaming driver): a no-move turn needs det_nostep and seven scalar records, yet left to the next
+// head it holds its lane out of a whole turn -- root inference and a search launch whose length is one tile's serial
+// chain of simulations, whatever the batch.  The flags pass plays up to kSpFfCap of them per game on the spot (longer
+// runs finish in the next heads: no result depends on the cap), so every launched lane-turn but those carries a
+// search.  Records are keyed by game number and step count, so they stay bit for bit; only the batched turn in
+// which a step happens changes, and `turns` shrinks.  The batch driver keeps one reference turn per launch.
+constexpr int kSpFfCap = 4;
 
 struct SpHead {
   uint32_t* legal;
@@ -158,9 +174,18 @@ struct SpHead {
   const float* s_weights;
   const float* s_value;
   muz_traj tr;
+  int ff_cap;             // STREAM: no-move turns the flags pass plays per game and launch (0: none, <= kSpFfCap)
 };
 
-// STREAM: the lane refill first (lane_game / next); otherwise lane g plays game g.
+// the game's lanes order their LDS accesses around lane 0's step (half a wave: no workgroup barrier)
+__device__ __forceinline__ void sp_wave_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// STREAM: the lane refill first (lane_game / next) and the fast-forward in the flags pass (o.ff_cap); otherwise
+// lane g plays game g, one reference turn per launch.
 // APPLY: the previous turn's apply first (k_sp_apply_g, on the rows this launch loads anyway): one launch and one
 // round trip of the rows fewer per turn.
 template <bool STREAM, bool APPLY>
@@ -170,7 +195,7 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
   __shared__ int8_t sboard[NG][kCells];
   __shared__ int8_t sstate[NG][kStateRow];
   __shared__ __attribute__((aligned(16))) uint8_t senc[NG][kEncStride];
-  __shared__ int s_gn[NG], s_f[NG], s_pre, s_reset;
+  __shared__ int s_gn[NG], s_f[NG], s_pre, s_reset, s_ffwd;
   const int t = threadIdx.x, lg = t / G, a = t % G;
   const int b = blockIdx.x, nb = gridDim.x;
   const int g0 = b * NG, games = min(NG, n - g0), g = g0 + lg;
@@ -190,7 +215,7 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
     s_gn[t] = -1;
     s_f[t] = 0;
   }
-  if (t == 0) s_reset = 0;
+  if (t == 0) s_reset = s_ffwd = 0;
   if (b == 0 && t < 4) o.counts_next[t] = 0;
   __syncthreads();
   if (APPLY) {
@@ -249,19 +274,45 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
     __syncthreads();
   }
   // flags: 1 = searches (a legal move), 2 = no move (no_step), 0 = idle
+  int tt = 0;   // the game's step count, carried through the fast-forward to the encode
   if (lg < games) {
     const int gn = STREAM ? s_gn[lg] : g;
-    const bool idle = sstate[lg][41] || (STREAM && (gn < 0 || idx[gn] >= T));
+    if (!STREAM || gn >= 0) tt = idx[gn];   // (every lane of the game, before its lane 0 advances it below)
+    const bool idle = sstate[lg][41] || (STREAM && (gn < 0 || tt >= T));
     uint32_t l = 0;
     int f = 0;
     if (!idle) {   // (uniform over the game's lanes)
       l = det_legal_g<G>(c, LdsLane{sstate[lg], sstate[lg][40], 0, 0}, BoardView{sboard[lg], 1}, a, t);
       f = l ? 1 : 2;
     }
+    int fc = f;   // what the compaction counts (== f but for a record filled below)
+    if constexpr (STREAM) {
+      // fast-forward: a game without a move plays its no_step turn here, on the rows in LDS, and is flagged again
+      // for the next player -- until it has a move, its record is full or the cap (then it keeps flag 2 and the
+      // next head applies it).  Local to the game's G lanes; every value below is uniform over them.
+      for (int it = 0; it < o.ff_cap && f == 2; ++it) {
+        sp_apply_game<G>(c, sstate[lg], sboard[lg], 2, 0, 0u, gn, tt, nullptr, nullptr, nullptr, o.tr, a);
+        ++tt;
+        if (a == 0) s_ffwd = 1;
+        sp_wave_sync();   // lane 0's action-set row and player, before the game's lanes read them
+        if (tt >= T) {
+          // Record full: idle for this turn, the next head's refill replaces the game.  While game numbers are
+          // left to hand out the lane still counts as active, or a turn in which every active lane ended like
+          // this would stop the driver (next[0] only grows: a stale value errs to one empty turn).
+          l = 0;
+          f = 0;
+          fc = __hip_atomic_load(next, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < num_games ? 3 : 0;
+          break;
+        }
+        l = det_legal_g<G>(c, LdsLane{sstate[lg], sstate[lg][40], 0, 0}, BoardView{sboard[lg], 1}, a, t);
+        fc = f = l ? 1 : 2;
+        sp_wave_sync();   // the lanes' reads, before lane 0 steps again
+      }
+    }
     if (a == 0) {
       o.legal[g] = l;
       o.flag[g] = f;
-      s_f[lg] = f;
+      s_f[lg] = fc;
     }
   }
   __syncthreads();
@@ -321,13 +372,13 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
                           (float)(v4 >> 24));
     }
     const int gn = STREAM ? s_gn[lg] : g;
-    uint4* to = reinterpret_cast<uint4*>(o.traj_obs + ((size_t)gn * T + idx[gn]) * C * kCells);
+    uint4* to = reinterpret_cast<uint4*>(o.traj_obs + ((size_t)gn * T + tt) * C * kCells);
     for (int q = a; q < C * 7 / 2; q += G) {
       const uint2 lo = det_obs_half(e, 2 * q, P, teams), hi = det_obs_half(e, 2 * q + 1, P, teams);
       to[q] = make_uint4(lo.x, lo.y, hi.x, hi.y);
     }
   }
-  if (APPLY || (STREAM && s_reset)) det_rows_store<NG>(c, st, g0, games, sboard, sstate, t, kHeadBlock);
+  if (APPLY || (STREAM && (s_reset | s_ffwd))) det_rows_store<NG>(c, st, g0, games, sboard, sstate, t, kHeadBlock);
 }
 
 __global__ void k_ss_init(DetConsts c, muz_detmadn_soa st, int32_t* lane_game, int32_t* next, int num_games, int W) {
@@ -338,12 +389,20 @@ __global__ void k_ss_init(DetConsts c, muz_detmadn_soa st, int32_t* lane_game, i
   det_reset_lane(c, st, l);
 }
 
+// The streaming driver's fast-forward cap: kSpFfCap unless MUZ_SP_FASTFORWARD says otherwise (read per call) --
+// 0 selects the head without fast-forward (A/B runs), 1 .. kSpFfCap that many no-move turns per game and launch
+// (tests of the cap path).
+static int sp_fastforward_cap() {
+  if (const char* e = getenv("MUZ_SP_FASTFORWARD")) return std::min(kSpFfCap, std::max(0, atoi(e)));
+  return kSpFfCap;
+}
+
 // The turn loop shared by the batch and the streaming driver.  Batch: lane g plays game g for at most T
 // turns.  Streaming (lane_game != null): lanes are refilled with the next game number when theirs ends,
 // until num_games games have been played.
 static int sp_turns(const DetConsts& c, const muz_net_w* w, const muz_search_cfg* cfg, muz_detmadn_soa st, muz_traj tr,
-                    int n, const SpWs& ws, const int32_t* lane_game, int num_games, int max_turns, muz_sp_stats* stats,
-                    hipStream_t s) {
+                    int n, const SpWs& ws, const int32_t* lane_game, int num_games, int max_turns, int ff_cap,
+                    muz_sp_stats* stats, hipStream_t s) {
   const int T = tr.max_steps;
   int rc = MUZ_OK;
   SearchArgs sa = make_search_args(*cfg);   // (sa.turn: set per turn below)
@@ -363,7 +422,7 @@ static int sp_turns(const DetConsts& c, const muz_net_w* w, const muz_search_cfg
     // (the ledger's counts reach the host through root inference's first kernel: no last-arrival ticket here)
     int32_t* const host_counts = led.device_slot(turn);
     const SpHead h{ws.legal, ws.flag, ws.list, ws.slot, counts, ws.counts + 4 * ((turn + 1) & 1), ws.legal_c, ws.obs,
-                   tr.obs, nullptr, ws.action, ws.weights, ws.value, tr};
+                   tr.obs, nullptr, ws.action, ws.weights, ws.value, tr, ff_cap};
     if (lane_game) {
       if (pending)
         k_sp_head<true, true><<<nbh, kHeadBlock, 0, s>>>(c, st, n, tr.idx, T, ws.lane_game, ws.next_game, num_games, h);
@@ -443,7 +502,7 @@ int muz_detmadn_selfplay(const muz_rules* rules, const muz_net_w* w, const muz_s
   // play_n_games_v3: batch_reset + zeroed buffers
   k_det_reset_sp<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
   if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
-  return sp_turns(c, w, cfg, st, tr, n, ws, nullptr, n, tr.max_steps, stats, s);
+  return sp_turns(c, w, cfg, st, tr, n, ws, nullptr, n, tr.max_steps, 0, stats, s);
 }
 
 int muz_detmadn_selfplay_stream(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg,
@@ -459,8 +518,8 @@ int muz_detmadn_selfplay_stream(const muz_rules* rules, const muz_net_w* w, cons
   // lane l starts game l (l < num_games); later games are handed out by the turn head's refill
   k_ss_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
   MUZ_HIP_RET(hipGetLastError());
-  return sp_turns(c, w, cfg, st, tr, n, ws, ws.lane_game, num_games, stream_max_turns(num_games, n, tr.max_steps), stats,
-                  s);
+  return sp_turns(c, w, cfg, st, tr, n, ws, ws.lane_game, num_games, stream_max_turns(num_games, n, tr.max_steps),
+                  sp_fastforward_cap(), stats, s);
 }
 
 }  // extern "C"

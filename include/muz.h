@@ -430,7 +430,8 @@ typedef struct muz_traj {
 /* Optional per-call statistics (host struct).  search_ms sums HIP-event durations of the search
  * kernel launches (events are recorded only when stats != NULL). */
 typedef struct muz_sp_stats {
-  int32_t turns;      /* batched turns that found an active game */
+  int32_t turns;      /* batched turns launched that found an active game (a stream that fast-forwards its
+                         no-move turns launches fewer of them than its games record turns) */
   int64_t searches;   /* MCTS searches run (sum over turns of games with a legal move) */
   double search_ms;   /* device time of the Gumbel-search launches */
   double total_ms;    /* device time of the whole call */
@@ -451,7 +452,12 @@ int muz_detmadn_selfplay(const muz_rules* rules /*host*/, const muz_net_w* w /*h
  * ends (done, or max_steps recorded) its lane takes the next game number (deterministic, lane order) and
  * is reset, so the search batch stays full until the last games.  traj is [num_games][T]; game k's
  * record, including its Gumbel noise (keyed by game number and the game's own step), is identical to
- * game k of a muz_detmadn_selfplay batch of num_games games. */
+ * game k of a muz_detmadn_selfplay batch of num_games games.
+ * A turn in which a game has no legal move (no_step) is played inside the turn head, up to 4 in a row per
+ * game and launch, so that game searches in the same launch instead of sitting it out: stats->turns, the
+ * launched turns, comes out smaller than the recorded turns of the longest lane; stats->searches and the
+ * records do not change.  Environment switch, read per call: MUZ_SP_FASTFORWARD=0 plays every no-move turn
+ * as a launched turn of its own (A/B runs), =N (1..4) caps the run played per launch at N (tests). */
 int muz_detmadn_selfplay_stream(const muz_rules* rules /*host*/, const muz_net_w* w /*host*/,
                                 const muz_search_cfg* cfg /*host*/, muz_detmadn_soa state, muz_traj traj,
                                 int32_t num_games, int32_t lanes, void* workspace, int64_t workspace_bytes,
