@@ -1051,6 +1051,7 @@ __device__ __forceinline__ void repr16(const AS4 muz_repr_w& R, const float* __r
   // kConvRowFloats), or -- D0_DONE -- its output, computed by k_dense0 into the scratch row after the maps
   if constexpr (D0_DONE) {
     pf_issue<NT64>(pf, &R.d1, Kg, 64);
+    static_assert(kThreads == 512, "repr16 D0_DONE: 512 threads copy the tile's 16 rows x 64 float4, 32 threads a row");
     const int rr = tid() >> 5, q = tid() & 31;   // 16 rows x 64 float4: 2 per thread
 #pragma unroll
     for (int i = 0; i < 2; ++i) {

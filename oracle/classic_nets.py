@@ -9,13 +9,15 @@ Flax semantics as in oracle.nets.  Parameter paths: the module's explicit names
 (``dynamics/act_embed/kernel`` ...); the four anonymous ResBlocks are ``ResBlock_0..1`` (action
 dynamics) and ``ResBlock_2..3`` (chance dynamics).
 Parity status: UNPINNED (flax absent, no classic checkpoints in the reference).
+Precision: fp32; inside ``precision(np.float64)`` (oracle.nets.precision, re-exported here) the same functions run in
+float64 end to end.
 """
 from __future__ import annotations
 
 import numpy as np
 
-from .nets import (F32, LATENT, SUPPORT, _resblock_shapes, dense, layer_norm, minmax, one_hot, pred_param_shapes,
-                   prediction, relu, repr_param_shapes, representation, resblock, softmax, sub)
+from .nets import (F32, LATENT, _P, _resblock_shapes, dense, layer_norm, minmax, one_hot, pred_param_shapes,
+                   precision, prediction, relu, repr_param_shapes, representation, resblock, softmax, sub, support)
 
 A_CLASSIC = 4
 CHANCE = 6
@@ -70,13 +72,13 @@ def _film_trunk(p, pre, rb0, x_in, e):
     """LN(input) * (1 + scale(e)) + shift(e) -> dense1/LN/relu -> dense2/LN/relu -> 2 ResBlocks -> proj,
     + input skip, min-max over features (lines 339-360 / 381-406)."""
     ln = layer_norm(p, f"{pre}_input_ln", x_in)
-    x = (ln * (F32(1.0) + dense(p, f"{pre}_film_scale", e)) + dense(p, f"{pre}_film_shift", e)).astype(F32)
+    x = (ln * (_P.dtype(1.0) + dense(p, f"{pre}_film_scale", e)) + dense(p, f"{pre}_film_shift", e)).astype(_P.dtype)
     x = relu(layer_norm(p, f"{pre}_ln1", dense(p, f"{pre}_dense1", x)))
     x = relu(layer_norm(p, f"{pre}_ln2", dense(p, f"{pre}_dense2", x)))
     for r in range(rb0, rb0 + 2):
         x = resblock(p, f"ResBlock_{r}", x)
     x = dense(p, f"{pre}_proj", x)
-    return minmax((x_in + x).astype(F32))
+    return minmax((x_in + x).astype(_P.dtype))
 
 
 def action_dynamics(params, latent, action, A: int = A_CLASSIC):
@@ -85,7 +87,7 @@ def action_dynamics(params, latent, action, A: int = A_CLASSIC):
     p = sub(params, "dynamics")
     oh = one_hot(action, A)
     e = relu(dense(p, "act_embed", oh))
-    after = _film_trunk(p, "act", 0, latent.astype(F32), e)
+    after = _film_trunk(p, "act", 0, latent.astype(_P.dtype), e)
     rl = dense(p, "reward_head", relu(dense(p, "reward_dense", np.concatenate([after, oh], -1))))
     dl = dense(p, "discount_head", relu(layer_norm(p, "discount_ln", dense(p, "discount_dense", latent))))
     cl = dense(p, "chance_head", after)
@@ -96,7 +98,7 @@ def chance_dynamics(params, afterstate, chance, C: int = CHANCE):
     """StochasticDynamicsNetwork4.chance_dynamics (373-408) -> next_state."""
     p = sub(params, "dynamics")
     e = relu(dense(p, "chance_embed", one_hot(chance, C)))
-    return _film_trunk(p, "chance", 2, afterstate.astype(F32), e)
+    return _film_trunk(p, "chance", 2, afterstate.astype(_P.dtype), e)
 
 
 def root_inference(params, obs):
@@ -110,8 +112,8 @@ def decision_recurrent(params, action, emb):
     """decision_recurrent_fn (414-432) -> (chance_logits, afterstate_value, afterstate, reward, discount);
     the reference concatenates reward / discount to the afterstate (258 floats)."""
     after, rl, cl, dl = action_dynamics(params, emb, action)
-    reward = (softmax(rl) * SUPPORT).sum(-1).astype(F32)
-    discount = (softmax(dl) * SUPPORT).sum(-1).astype(F32)
+    reward = (softmax(rl) * support()).sum(-1).astype(_P.dtype)
+    discount = (softmax(dl) * support()).sum(-1).astype(_P.dtype)
     _, v = prediction(params, after)
     return cl, v[:, 0], after, reward, discount
 

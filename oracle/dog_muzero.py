@@ -81,6 +81,9 @@ def init_params(seed: int = 0, randomize_affine: bool = False) -> dict:
     return ON.init_params(NUM_CHANNELS, NUM_ACTIONS, seed=seed, randomize_affine=randomize_affine, head="layernorm")
 
 
+precision = ON.precision   # ``with precision(np.float64):`` -- the networks below in float64 (oracle/nets.py)
+
+
 def root_inference(params, obs):
     """root_inference_fn for the slice: RepresentationNetwork -> PredictionNetwork4 (A = 806)."""
     return ON.root_inference(params, obs)

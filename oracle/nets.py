@@ -9,15 +9,51 @@ Flax 0.12.1 semantics (not vendored in the reference, restated from its public s
 Parity status: UNPINNED (flax is absent and the reference's .pkl checkpoints are missing);
 the GPU kernels are checked against this restatement within a stated fp32 tolerance.
 
+Precision: fp32 by default; ``with precision(np.float64):`` runs the same functions in float64 end to end (the
+GPU tests' exact-arithmetic reference, tests/_nets64.py).
+
 Parameters are a flat dict keyed by Flax paths, e.g. ``dynamics/ResBlock_0/Dense_1/kernel``.
 """
 from __future__ import annotations
+
+import contextlib
 
 import numpy as np
 
 LATENT = 256
 EPS_LN = 1e-6
 F32 = np.float32
+
+
+class _P:
+    """The precision the layers below compute in (see ``precision``); fp32 unless switched."""
+    dtype = np.float32
+
+
+@contextlib.contextmanager
+def precision(dtype):
+    """Evaluate the restatements of this file, oracle/classic_nets.py and oracle/dog_muzero.py in ``dtype``
+    (np.float32, the default, or np.float64) inside the block: the same functions end to end -- parameters, inputs,
+    one_hot, the min-max / LayerNorm constants, SUPPORT, tanh, softmax -- so the float64 run is the fp32 yardstick's
+    exact-arithmetic twin, not a second implementation.  Returned arrays have that dtype."""
+    dtype = np.dtype(dtype).type
+    if dtype not in (np.float32, np.float64):
+        raise ValueError(f"precision: float32 or float64, not {dtype}")
+    prev, _P.dtype = _P.dtype, dtype
+    try:
+        yield
+    finally:
+        _P.dtype = prev
+
+
+def _w(p, key):
+    """Parameter ``key`` in the precision in force (the stored fp32 array itself by default)."""
+    return p[key].astype(_P.dtype, copy=False)
+
+
+def support():
+    """The reward / discount support {-1, 0, 1} in the precision in force."""
+    return SUPPORT.astype(_P.dtype, copy=False)
 
 
 # ---------------------------------------------------------------- parameter layout
@@ -124,33 +160,33 @@ def sub(params: dict, prefix: str) -> dict:
 
 # ---------------------------------------------------------------- layers
 def dense(p, name, x):
-    return (x.astype(F32) @ p[f"{name}/kernel"] + p[f"{name}/bias"]).astype(F32)
+    return (x.astype(_P.dtype) @ _w(p, f"{name}/kernel") + _w(p, f"{name}/bias")).astype(_P.dtype)
 
 
 def layer_norm(p, name, x):
-    x = x.astype(F32)
-    mean = x.mean(-1, keepdims=True, dtype=F32)
-    mean2 = (x * x).mean(-1, keepdims=True, dtype=F32)
-    var = np.maximum(F32(0.0), mean2 - mean * mean)
-    mul = (F32(1.0) / np.sqrt(var + F32(EPS_LN))).astype(F32) * p[f"{name}/scale"]
-    return ((x - mean) * mul + p[f"{name}/bias"]).astype(F32)
+    x = x.astype(_P.dtype)
+    mean = x.mean(-1, keepdims=True, dtype=_P.dtype)
+    mean2 = (x * x).mean(-1, keepdims=True, dtype=_P.dtype)
+    var = np.maximum(_P.dtype(0.0), mean2 - mean * mean)
+    mul = (_P.dtype(1.0) / np.sqrt(var + _P.dtype(EPS_LN))).astype(_P.dtype) * _w(p, f"{name}/scale")
+    return ((x - mean) * mul + _w(p, f"{name}/bias")).astype(_P.dtype)
 
 
 def relu(x):
-    return np.maximum(x, F32(0.0))
+    return np.maximum(x, _P.dtype(0.0))
 
 
 def conv1d_same(p, name, x):
     """Flax Conv, 1-D NWC, padding 'SAME', stride 1 (cross-correlation)."""
-    k = p[f"{name}/kernel"]        # (K, Cin, Cout)
+    k = _w(p, f"{name}/kernel")        # (K, Cin, Cout)
     K = k.shape[0]
     pl = (K - 1) // 2
     pr = K - 1 - pl
     B, W, Cin = x.shape
-    xp = np.zeros((B, W + K - 1, Cin), F32)
+    xp = np.zeros((B, W + K - 1, Cin), _P.dtype)
     xp[:, pl:pl + W] = x
     cols = np.concatenate([xp[:, d:d + W, :] for d in range(K)], axis=-1)   # (B, W, K*Cin)
-    return (cols @ k.reshape(K * Cin, -1) + p[f"{name}/bias"]).astype(F32)
+    return (cols @ k.reshape(K * Cin, -1) + _w(p, f"{name}/bias")).astype(_P.dtype)
 
 
 def resblock(p, name, x):
@@ -163,7 +199,7 @@ def resblock(p, name, x):
 def minmax(x):
     lo = x.min(-1, keepdims=True)
     hi = x.max(-1, keepdims=True)
-    return ((x - lo) / (hi - lo + F32(1e-8))).astype(F32)
+    return ((x - lo) / (hi - lo + _P.dtype(1e-8))).astype(_P.dtype)
 
 
 # ---------------------------------------------------------------- networks
@@ -172,7 +208,7 @@ def representation(params: dict, obs: np.ndarray) -> np.ndarray:
     ``representation/LayerNorm_7`` entry it is the DOG RepresentationNetwork (MuZero_DOG/muzero_dog.py:25-83):
     the same trunk, LayerNorm instead of min-max after the last Dense (80-81)."""
     p = sub(params, "representation")
-    x = obs.astype(F32)
+    x = obs.astype(_P.dtype)
     sp = np.transpose(x[:, :6, :], (0, 2, 1))            # (B, 56, 6)
     g = x[:, 6:, 0]                                      # (B, C-6)
     sp = relu(layer_norm(p, "LayerNorm_0", conv1d_same(p, "Conv_0", sp)))
@@ -192,7 +228,7 @@ def representation(params: dict, obs: np.ndarray) -> np.ndarray:
 
 def one_hot(a, n):
     a = np.asarray(a)
-    out = np.zeros(a.shape + (n,), F32)
+    out = np.zeros(a.shape + (n,), _P.dtype)
     ok = (a >= 0) & (a < n)
     out[ok, a[ok]] = 1.0      # jax.nn.one_hot: out-of-range (e.g. -1) -> all-zero row
     return out
@@ -208,13 +244,13 @@ def dynamics(params: dict, latent: np.ndarray, action: np.ndarray, A: int | None
     ln = layer_norm(p, "LayerNorm_0", latent)
     scale = dense(p, "Dense_1", e)
     shift = dense(p, "Dense_2", e)
-    x = (ln * (F32(1.0) + scale) + shift).astype(F32)
+    x = (ln * (_P.dtype(1.0) + scale) + shift).astype(_P.dtype)
     x = relu(layer_norm(p, "LayerNorm_1", dense(p, "Dense_3", x)))
     x = relu(layer_norm(p, "LayerNorm_2", dense(p, "Dense_4", x)))
     for r in range(2):
         x = resblock(p, f"ResBlock_{r}", x)
     x = dense(p, "Dense_5", x)
-    nxt = minmax((latent + x).astype(F32))
+    nxt = minmax((latent + x).astype(_P.dtype))
     ri = np.concatenate([nxt, oh], -1)
     rl = dense(p, "reward_head", relu(dense(p, "Dense_6", ri)))
     dl = dense(p, "discount_head", relu(dense(p, "Dense_7", ri)))
@@ -232,14 +268,14 @@ def prediction(params: dict, latent: np.ndarray):
     logits = dense(p, "Dense_2", pol)
     v = relu(layer_norm(p, "LayerNorm_3", dense(p, "Dense_3", x)))
     v = relu(dense(p, "Dense_4", v))
-    v = np.tanh(dense(p, "Dense_5", v)).astype(F32)
+    v = np.tanh(dense(p, "Dense_5", v)).astype(_P.dtype)
     return logits, v
 
 
 def softmax(x, axis=-1):
-    x = x.astype(F32)
+    x = x.astype(_P.dtype)
     u = np.exp(x - x.max(axis, keepdims=True))
-    return (u / u.sum(axis, keepdims=True)).astype(F32)
+    return (u / u.sum(axis, keepdims=True)).astype(_P.dtype)
 
 
 SUPPORT = np.array([-1.0, 0.0, 1.0], F32)
@@ -257,6 +293,6 @@ def recurrent_inference(params, action, emb):
     -> (reward, discount, prior_logits, value, next_embedding)."""
     nxt, rl, dl = dynamics(params, emb, action)
     logits, v = prediction(params, nxt)
-    reward = (softmax(rl) * SUPPORT).sum(-1).astype(F32)
-    discount = (softmax(dl) * SUPPORT).sum(-1).astype(F32)
+    reward = (softmax(rl) * support()).sum(-1).astype(_P.dtype)
+    discount = (softmax(dl) * support()).sum(-1).astype(_P.dtype)
     return reward, discount, logits, v[:, 0], nxt
