@@ -63,6 +63,34 @@ int launch_gumbel_search(const muz_net_w& w, const SearchArgs& sa, const float* 
 
 int64_t search_workspace_bytes(int n, int S);
 
+// PUCT MuZero search for det-MADN (puct_search.hip); its workspace is the Gumbel search's (search_workspace_bytes)
+struct PuctArgs {
+  int S, D, qtransform;
+  float min_value, max_value, dir_frac, dir_alpha, pb_c_init, pb_c_base, temperature;
+  unsigned long long seed;
+  int turn;
+};
+static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
+  PuctArgs pa;
+  pa.S = cfg.num_simulations;
+  pa.D = cfg.max_depth;
+  pa.qtransform = cfg.qtransform;
+  pa.min_value = cfg.min_value;
+  pa.max_value = cfg.max_value;
+  pa.dir_frac = cfg.dirichlet_fraction;
+  pa.dir_alpha = cfg.dirichlet_alpha;
+  pa.pb_c_init = cfg.pb_c_init;
+  pa.pb_c_base = cfg.pb_c_base;
+  pa.temperature = cfg.temperature;
+  pa.seed = cfg.seed;
+  pa.turn = cfg.turn;
+  return pa;
+}
+int launch_puct_search(const muz_net_w& w, const PuctArgs& pa, const float* root_logits, const float* root_value,
+                       const float* root_emb, const uint32_t* legal, const float* dirichlet, const float* gumbel,
+                       const int32_t* game_id, int n, void* workspace, int32_t* action, float* weights, float* value,
+                       hipStream_t s);
+
 // Stochastic MuZero (stochastic.hip)
 struct SArgs {
   int S, D, A;

@@ -57,24 +57,7 @@ using TreeWs = NarrowTree<kAPad>;
 //    a_{j+16} for j < 8, then ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7));
 //  * exp correctly rounded: evaluated in float64 and rounded once (numpy's float32 exp and the device's expf
 //    are each ~1 ulp off in different places; the oracle rounds the float64 exp the same way).
-enum { DPP_ROW_ROR8 = 0x128 };
-__device__ __forceinline__ float row_sum24(float v) {
-  static_assert(kRowLanes == 32, "row_sum24: one game per 32 lanes");
-  if (tsub() >= 24) v = -0.0f;                  // the additive identity for every x, -0 included
-  v = v + dpp<DPP_ROW_ROR8>(v);                 // a_j + a_{j+8} (lanes 16..23: a_{16+j} + -0)
-  const LoHi<float> p = swap16(v);
-  v = p.lo + p.hi;                              // r_j = (a_j + a_{j+8}) + a_{j+16} in lanes j, j+8, j+16, j+24
-  v = v + dpp<DPP_XOR1>(v);                     // r0 + r1 | r2 + r3 | ...
-  v = v + dpp<DPP_XOR2>(v);                     // (r0 + r1) + (r2 + r3) | (r4 + r5) + (r6 + r7)
-  return v + dpp<DPP_HALF_MIRROR>(v);           // lane i <-> 7 - i: the two halves
-}
-
-// One child edge of the current node, held by lane `a` of the game's 32 lanes (ok = a < A).
-struct Kid {
-  float prior, value, reward, disc;
-  int visits, index;
-  bool ok;
-};
+// (row_sum24 and Kid: tree.hpp, shared with k_puct_search)
 
 // qtransform_completed_by_mix_value (value_scale, maxvisit_init, rescale, mixed value, eps 1e-8).
 __device__ __forceinline__ float completed_q(const Kid& k, float raw, const SearchArgs& sa, int& sumv, float& pmax) {

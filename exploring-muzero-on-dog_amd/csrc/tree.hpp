@@ -1,4 +1,4 @@
-// The tree machinery the persistent search kernels share (k_gumbel_search, k_stochastic_search, k_dog_search): one
+// The tree machinery the persistent search kernels share (k_gumbel_search, k_puct_search, k_stochastic_search, k_dog_search): one
 // game per kRowLanes lanes, node scalars and the current path in LDS, children arrays and node embeddings in the
 // workspace.  The limits (kMaxSims, kMaxNodes, kMaxDepth) sit beside SearchArgs in launch.hpp, where the host entry
 // points read them too.
@@ -44,6 +44,29 @@ __device__ __forceinline__ void row_argmax(float& v, int& i) {
 // exp and the device's expf are each ~1 ulp off in different places)
 // (A/B, profiles/r4k_dog_ab.log: a float __expf in its place -- wrong rounding -- was 22-27 % faster per DOG search)
 __device__ __forceinline__ float exp_cr(float x) { return (float)exp((double)x); }
+// log correctly rounded, the same way (k_puct_search: the root's noisy logits, pb_c, the final temperature logits)
+__device__ __forceinline__ float log_cr(float x) { return (float)log((double)x); }
+
+// A sum over the 24 det-MADN actions in numpy's pairwise order for a contiguous row of 24 (see search.hip's note on
+// the tree arithmetic), and one child edge of a node (k_gumbel_search, k_puct_search)
+enum { DPP_ROW_ROR8 = 0x128 };
+__device__ __forceinline__ float row_sum24(float v) {
+  static_assert(kRowLanes == 32, "row_sum24: one game per 32 lanes");
+  if (tsub() >= 24) v = -0.0f;                  // the additive identity for every x, -0 included
+  v = v + dpp<DPP_ROW_ROR8>(v);                 // a_j + a_{j+8} (lanes 16..23: a_{16+j} + -0)
+  const LoHi<float> p = swap16(v);
+  v = p.lo + p.hi;                              // r_j = (a_j + a_{j+8}) + a_{j+16} in lanes j, j+8, j+16, j+24
+  v = v + dpp<DPP_XOR1>(v);                     // r0 + r1 | r2 + r3 | ...
+  v = v + dpp<DPP_XOR2>(v);                     // (r0 + r1) + (r2 + r3) | (r4 + r5) + (r6 + r7)
+  return v + dpp<DPP_HALF_MIRROR>(v);           // lane i <-> 7 - i: the two halves
+}
+
+// One child edge of the current node, held by lane `a` of the game's 32 lanes (ok = a < A).
+struct Kid {
+  float prior, value, reward, disc;
+  int visits, index;
+  bool ok;
+};
 
 // seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.
 __device__ __forceinline__ int considered_visit(int m, int S, int idx) {

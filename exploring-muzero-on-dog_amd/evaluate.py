@@ -79,9 +79,11 @@ def winners(env: E.DetMADNState, teams: bool) -> torch.Tensor:
 @torch.no_grad()
 def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4, num_simulations: int = 50,
                    max_depth: int = 25, seed: int = 42, max_turns: int = 2000, rules: dict | None = None,
-                   device="cuda") -> dict:
+                   device="cuda", *, search: str = "gumbel") -> dict:
     """One batch of games, agent at seat 0 (+2 with teams), random elsewhere.  ``net=None`` makes the
-    agent random too (the baseline).  Returns wins at seat 0, per-seat wins and pins in goal."""
+    agent random too (the baseline).  ``search="puct"``: the agent searches with mcts.muzero_policy at temperature 0
+    without root noise.  Returns wins at seat 0, per-seat wins and pins in goal."""
+    skw = _search_kwargs(search)
     r = dict(RULES if rules is None else rules)
     teams = bool(r.get("enable_teams", False)) and num_players == 4
     P = num_players
@@ -111,7 +113,7 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
             sub = _sub(env, ag)
             obs = E.encode_board(sub)
             out, _ = M.muzero_mcts(net, obs, bits[ag], num_simulations, max_depth, 0.0, seed=seed, turn=turn,
-                                       workspace=ws)
+                                       workspace=ws, **skw)
             act[ag] = out.action
         if rd.numel():
             act[rd] = random_legal(bits[rd], gen)
@@ -131,12 +133,13 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
             "finished": int(env.done.sum()), "pins_in_goal": in_goal.tolist()}
 
 
-def test_agent_vs_random(net: N.DeviceNet | None, num_games: int, batch_size: int = 1024, seed: int = 42,
-                         **kw) -> tuple:
-    """evaluate_agent.py:383-472 -> (wins at seat 0, mean pins in goal per seat)."""
+def test_agent_vs_random(net: N.DeviceNet | None, num_games: int, batch_size: int = 1024, seed: int = 42, *,
+                         search: str = "gumbel", **kw) -> tuple:
+    """evaluate_agent.py:383-472 -> (wins at seat 0, mean pins in goal per seat); ``search``: "gumbel" or "puct"
+    (play_vs_random)."""
     wins, prog, done = 0, None, 0
     for b in range(0, num_games, batch_size):
-        r = play_vs_random(net, min(batch_size, num_games - b), seed=seed + b, **kw)
+        r = play_vs_random(net, min(batch_size, num_games - b), seed=seed + b, search=search, **kw)
         wins += r["wins"]
         p = torch.tensor(r["pins_in_goal"]) * r["games"]
         prog = p if prog is None else prog + p
@@ -164,6 +167,16 @@ def compare_agents_statistically(net1, net2, num_games: int = 1000, batch_size: 
 
 
 # ---- four seats: evaluate_agent_parallel (evaluate_agent.py:253-311, 715-960) ----------------------------
+def _search_kwargs(search: str) -> dict:
+    """muzero_mcts keywords of an evaluation seat's search: today's Gumbel call, or the PUCT muzero_policy without
+    root noise (the classical MuZero evaluation agent at temperature 0)."""
+    if search == "gumbel":
+        return {}
+    if search == "puct":
+        return {"policy": "puct", "dirichlet_fraction": 0.0}
+    raise ValueError(f"unknown search {search!r} ('gumbel' or 'puct')")
+
+
 def policy_action(env: E.DetMADNState, legal: torch.Tensor, mode: str, seed: int, turn: int, agent: dict | None = None,
                   game_id: torch.Tensor | None = None) -> torch.Tensor:
     """The random ('random_agent') or rule-based ('rule_based_agent') action of every game (int32 [B], -1
@@ -218,14 +231,16 @@ def calculate_progress(env: E.DetMADNState, must_traverse_start: bool = False) -
 @torch.no_grad()
 def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int = 100, max_depth: int = 50,
                             temperature: float = 0.0, seed: int = 0, rules: dict | None = None, max_turns: int = 2000,
-                            rule_agent: dict | None = None, device="cuda") -> dict:
+                            rule_agent: dict | None = None, device="cuda", *, search: str = "gumbel") -> dict:
     """evaluate_agent_parallel (evaluate_agent.py:253-311): `agents` = the four seats (player indices 0-3),
     each a DeviceNet, None (a MuZero agent with randomly initialised params), 'rule_based_agent' or
     'random_agent'.  4 x batch_size games, block i started by player i (jnp.repeat(arange(4), batch_size)),
-    at most 2000 turns; MuZero seats search with S / D / temperature (evaluate_agent.py:938-940 defaults).
+    at most 2000 turns; MuZero seats search with S / D / temperature (evaluate_agent.py:938-940 defaults) -- the
+    Gumbel search, or with ``search="puct"`` mcts.muzero_policy without root noise.
     Returns winners[start][player] and average_progress[start][player] as the reference prints them, plus
     their totals (wins per player, progress per player = column sum / 4)."""
     r = dict(RULES if rules is None else rules)
+    skw = _search_kwargs(search)
     P = 4
     C = E.num_channels(P)
     nets = []
@@ -265,7 +280,7 @@ def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int =
                 idx = sel.nonzero().flatten()
                 sub = _sub(env, idx)
                 out, _ = M.muzero_mcts(a, E.encode_board(sub), bits[idx], num_simulations, max_depth, temperature,
-                                       seed=seed, turn=turn, workspace=ws)
+                                       seed=seed, turn=turn, workspace=ws, **skw)
                 act[idx] = out.action
         step = mover.nonzero().flatten()
         if step.numel():

@@ -221,6 +221,19 @@ class MuzStochCfg(ctypes.Structure):
                 ("turn", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
+# muz_puct_cfg.qtransform
+MUZ_QT_MIN_MAX = 0
+MUZ_QT_PARENT_SIBLINGS = 1
+
+
+class MuzPuctCfg(ctypes.Structure):
+    _fields_ = [("num_simulations", ctypes.c_int32), ("max_depth", ctypes.c_int32), ("qtransform", ctypes.c_int32),
+                ("min_value", ctypes.c_float), ("max_value", ctypes.c_float),
+                ("dirichlet_fraction", ctypes.c_float), ("dirichlet_alpha", ctypes.c_float),
+                ("pb_c_init", ctypes.c_float), ("pb_c_base", ctypes.c_float), ("temperature", ctypes.c_float),
+                ("turn", ctypes.c_int32), ("seed", ctypes.c_uint64)]
+
+
 class MuzSearchCfg(ctypes.Structure):
     _fields_ = [("num_simulations", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("max_num_considered", ctypes.c_int32), ("value_scale", ctypes.c_float),
@@ -353,6 +366,8 @@ SIGNATURES = {
     "muz_search_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),
     "muz_gumbel_search": (ctypes.c_int, [ctypes.POINTER(MuzNetW), ctypes.POINTER(MuzSearchCfg), vp, vp, vp, vp,
                                          vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "muz_puct_search": (ctypes.c_int, [ctypes.POINTER(MuzNetW), ctypes.POINTER(MuzPuctCfg), vp, vp, vp, vp, vp,
+                                       vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
     "muz_selfplay_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),
     "muz_detmadn_selfplay": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzNetW),
                                             ctypes.POINTER(MuzSearchCfg), MuzDetSoA, MuzTraj, ctypes.c_int32, vp,

@@ -1,7 +1,10 @@
-"""Gumbel MuZero search on the GPU: run_muzero_mcts (MuZero_det_MADN/muzero_deterministic_madn.py:663-704).
+"""MuZero search on the GPU: run_muzero_mcts (MuZero_det_MADN/muzero_deterministic_madn.py:663-704).
 
 The whole ``mctx.gumbel_muzero_policy`` call (S simulations of select / expand / backup) is one
-persistent HIP kernel (csrc/search.hip); the root inference runs first (csrc/nets.hip).
+persistent HIP kernel (csrc/search.hip); the root inference runs first (csrc/nets.hip).  The reference's
+second policy, the ``mctx.muzero_policy`` call it keeps commented (685-697: PUCT, Dirichlet root noise,
+visit-count weights), is ``muzero_policy`` here: another persistent kernel (csrc/puct_search.hip) on the same
+workspace, chosen with ``policy="puct"``.
 """
 from __future__ import annotations
 
@@ -77,12 +80,76 @@ def gumbel_muzero_policy(net: _N.DeviceNet, root_logits, root_value, root_embedd
     return PolicyOutput(action, weights), value
 
 
+QTRANSFORMS = {"min_max": _L.MUZ_QT_MIN_MAX, "parent_and_siblings": _L.MUZ_QT_PARENT_SIBLINGS}
+
+
+def make_puct_cfg(num_simulations, max_depth, temperature=1.0, qtransform="min_max", min_value=-1.0, max_value=1.0,
+                  dirichlet_fraction=0.25, dirichlet_alpha=0.3, pb_c_init=1.25, pb_c_base=19652.0, seed=0, turn=0):
+    """muz_puct_cfg with the constants of the reference's commented mctx.muzero_policy call (685-697) and mctx's
+    defaults for what that call leaves out (pb_c_init, pb_c_base)."""
+    if qtransform not in QTRANSFORMS:
+        raise ValueError(f"unknown qtransform {qtransform!r} (one of {sorted(QTRANSFORMS)})")
+    c = _L.MuzPuctCfg()
+    c.num_simulations = int(num_simulations)
+    c.max_depth = int(max_depth)
+    c.qtransform = QTRANSFORMS[qtransform]
+    c.min_value = float(min_value)
+    c.max_value = float(max_value)
+    c.dirichlet_fraction = float(dirichlet_fraction)
+    c.dirichlet_alpha = float(dirichlet_alpha)
+    c.pb_c_init = float(pb_c_init)
+    c.pb_c_base = float(pb_c_base)
+    c.temperature = float(temperature)
+    c.seed = int(seed) & ((1 << 64) - 1)
+    c.turn = int(turn)
+    return c
+
+
+def muzero_policy(net: _N.DeviceNet, root_logits, root_value, root_embedding, legal_bits, num_simulations, max_depth,
+                  temperature=1.0, *, qtransform="min_max", min_value=-1.0, max_value=1.0, dirichlet_fraction=0.25,
+                  dirichlet_alpha=0.3, pb_c_init=1.25, pb_c_base=19652.0, dirichlet=None, gumbel=None, seed=0, turn=0,
+                  game_id=None, workspace: SearchWorkspace | None = None):
+    """mctx.muzero_policy as the reference's commented call sets it (muzero_deterministic_madn.py:685-697): PUCT
+    selection with qtransform_by_min_max(-1, 1) (``qtransform="parent_and_siblings"``: mctx's default), Dirichlet
+    root noise 0.25 / 0.3, visit-count action weights, ``temperature`` on the final draw (0: a most-visited action).
+    ``dirichlet`` / ``gumbel`` = explicit root noise / final Gumbel draws [B, A], or None to draw them on device from
+    (seed, game_id, turn).  Returns (PolicyOutput, root_value = search_tree.summary().value)."""
+    lib = _L.load()
+    B = root_logits.shape[0]
+    dev = root_logits.device
+    if workspace is None or not workspace.fits(B, num_simulations):
+        workspace = SearchWorkspace(B, num_simulations, dev)
+    cfg = make_puct_cfg(num_simulations, max_depth, temperature, qtransform, min_value, max_value, dirichlet_fraction,
+                        dirichlet_alpha, pb_c_init, pb_c_base, seed, turn)
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, net.A), dtype=torch.float32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    dn = None if dirichlet is None else dirichlet.to(device=dev, dtype=torch.float32).contiguous()
+    g = None if gumbel is None else gumbel.to(device=dev, dtype=torch.float32).contiguous()
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).contiguous()
+    lb = legal_bits.to(device=dev, dtype=torch.int32).contiguous()
+    _L.check(lib.muz_puct_search(net.w, cfg, _L.ptr(root_logits.contiguous()), _L.ptr(root_value.contiguous()),
+                                 _L.ptr(root_embedding.contiguous()), _L.ptr(lb), _L.ptr(dn), _L.ptr(g), _L.ptr(gid), B,
+                                 _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action), _L.ptr(weights),
+                                 _L.ptr(value), _L.stream_ptr()), "muz_puct_search")
+    return PolicyOutput(action, weights), value
+
+
 def muzero_mcts(net: _N.DeviceNet, observations, legal_bits, num_simulations, max_depth, temperature,
-                gumbel=None, seed=0, turn=0, workspace: SearchWorkspace | None = None):
+                gumbel=None, seed=0, turn=0, workspace: SearchWorkspace | None = None, *, policy="gumbel",
+                **policy_kwargs):
     """Device-native form of run_muzero_mcts: a DeviceNet, device observations and the 24-bit legal mask
-    per game (what the self-play / evaluation loops hold); root inference + Gumbel search."""
+    per game (what the self-play / evaluation loops hold); root inference + Gumbel search, or with
+    ``policy="puct"`` root inference + muzero_policy (``policy_kwargs``: its keyword arguments)."""
+    if policy not in ("gumbel", "puct"):
+        raise ValueError(f"unknown policy {policy!r} ('gumbel' or 'puct')")
+    if policy == "gumbel" and policy_kwargs:
+        raise TypeError(f"policy='gumbel' takes no {sorted(policy_kwargs)}")
     scratch = workspace.scratch if workspace is not None else None
     logits, value, emb = _N.root_inference_fn(net, observations, scratch)
+    if policy == "puct":
+        return muzero_policy(net, logits, value, emb, legal_bits, num_simulations, max_depth, temperature,
+                             gumbel=gumbel, seed=seed, turn=turn, workspace=workspace, **policy_kwargs)
     return gumbel_muzero_policy(net, logits, value, emb, legal_bits, num_simulations, max_depth, temperature,
                                 gumbel=gumbel, seed=seed, turn=turn, workspace=workspace)
 
@@ -96,7 +163,8 @@ def invalid_to_bits(invalid_actions) -> torch.Tensor:
     return ((~inv).to(torch.int64) << sh).sum(1).to(torch.int32)
 
 
-def run_muzero_mcts(params, rng_key, observations, invalid_actions, num_simulations, max_depth, temperature):
+def run_muzero_mcts(params, rng_key, observations, invalid_actions, num_simulations, max_depth, temperature, *,
+                    policy="gumbel", **policy_kwargs):
     """run_muzero_mcts (MuZero_det_MADN/muzero_deterministic_madn.py:663-704), reference signature.
 
     ``params``: init_muzero_params' nested Flax dict (or a flat dict / DeviceNet, see nets.as_device_net);
@@ -107,10 +175,19 @@ def run_muzero_mcts(params, rng_key, observations, invalid_actions, num_simulati
 
     Kernel limits (k_gumbel_search; every reference call site is inside them: S = 50 / 100, D = 25 / 50):
     num_simulations 1..100, max_depth 1..64, 24 actions (det-MADN), max_num_considered_actions 16 (mctx's
-    default); outside them muz_gumbel_search returns MUZ_E_UNSUPPORTED and this raises MuzError."""
+    default); outside them muz_gumbel_search returns MUZ_E_UNSUPPORTED and this raises MuzError.
+
+    ``policy="puct"`` runs the reference's other policy instead, the mctx.muzero_policy call it keeps commented
+    (685-697), with that call's constants: PUCT selection, qtransform_by_min_max(-1, 1), Dirichlet root noise
+    0.25 / 0.3, visit-count action_weights, ``temperature`` on the final draw (muzero_policy above; ``policy_kwargs``
+    override its keyword arguments, e.g. ``dirichlet_fraction=0`` or ``qtransform="parent_and_siblings"``).  Its limits
+    (k_puct_search): num_simulations 1..100, max_depth 1..64, 24 actions, max_value > min_value, dirichlet_fraction in
+    [0, 1], dirichlet_alpha > 0, pb_c_base > 0, temperature >= 0; outside them muz_puct_search returns
+    MUZ_E_UNSUPPORTED and this raises MuzError."""
     dev = torch.device("cuda")
     net = _N.as_device_net(params, device=dev)
     obs = observations if isinstance(observations, torch.Tensor) else torch.from_numpy(np.asarray(observations))
     obs = obs.to(device=dev, dtype=torch.float32)
     bits = invalid_to_bits(invalid_actions).to(dev)
-    return muzero_mcts(net, obs, bits, num_simulations, max_depth, temperature, seed=_N.rng_key_to_seed(rng_key))
+    return muzero_mcts(net, obs, bits, num_simulations, max_depth, temperature, seed=_N.rng_key_to_seed(rng_key),
+                       policy=policy, **policy_kwargs)

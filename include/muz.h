@@ -410,6 +410,46 @@ int muz_gumbel_search(const muz_net_w* w /*host*/, const muz_search_cfg* cfg /*h
                       int64_t workspace_bytes, int32_t* action, float* action_weights, float* root_value_out,
                       void* stream);
 
+/* ---- PUCT MuZero search: the second policy of run_muzero_mcts (muzero_deterministic_madn.py:685-697, the
+ * mctx.muzero_policy call the reference keeps commented beside the Gumbel one) -------------------------------
+ * Restates mctx 0.0.6 policies.py muzero_policy (_add_dirichlet_noise, _get_logits_from_probs,
+ * _mask_invalid_actions, _apply_temperature), action_selection.py muzero_action_selection, qtransforms.py
+ * qtransform_by_min_max / qtransform_by_parent_and_siblings and search.py search / simulate / expand / backward. */
+#define MUZ_QT_MIN_MAX 0           /* qtransform_by_min_max(min_value, max_value): the reference's commented call */
+#define MUZ_QT_PARENT_SIBLINGS 1   /* qtransform_by_parent_and_siblings (mctx's default), epsilon 1e-8 */
+typedef struct muz_puct_cfg {
+  int32_t num_simulations;      /* S, 1..100 */
+  int32_t max_depth;            /* D, 1..64 */
+  int32_t qtransform;           /* MUZ_QT_MIN_MAX or MUZ_QT_PARENT_SIBLINGS */
+  float min_value;              /* -1 (MUZ_QT_MIN_MAX only) */
+  float max_value;              /* 1  (MUZ_QT_MIN_MAX only) */
+  float dirichlet_fraction;     /* 0.25; 0 = no root noise (evaluation) */
+  float dirichlet_alpha;        /* 0.3 */
+  float pb_c_init;              /* 1.25 */
+  float pb_c_base;              /* 19652 */
+  float temperature;            /* of the final draw; 0 = a most-visited action */
+  int32_t turn;                 /* counter-RNG stream */
+  uint64_t seed;
+} muz_puct_cfg;
+
+/* Batched muzero_policy on det-MADN (24 actions).  The workspace is the Gumbel search's: at least
+ * muz_search_workspace_bytes(n, cfg') bytes for a muz_search_cfg cfg' with the same num_simulations, so one
+ * workspace serves both policies.  legal_bits: 24-bit valid_action masks.  dirichlet [n][24] / gumbel [n][24] are the
+ * root noise sample and the Gumbel draws of the final categorical; NULL = the engine's counter RNG keyed by (seed,
+ * game_id, turn) (Gamma(alpha) sampler normalised over the actions / -log(-log U)).  The 1e-7 tie-break uniforms
+ * always come from the counter RNG (seed, game, turn, sim, depth, action).  game_id [n] (nullable: identity) only
+ * feeds those counters.
+ * Outputs: action [n], action_weights [n][24] (root visit fractions), root_value [n] = search_tree.summary().value
+ * (the root's backed-up value, not clipped).
+ * MUZ_E_UNSUPPORTED: num_actions != 24, S or D outside the limits, an unknown qtransform, max_value <= min_value,
+ * dirichlet_fraction outside [0, 1], dirichlet_alpha <= 0, pb_c_base <= 0, temperature < 0.  MUZ_E_INVALID: a null
+ * pointer or a short workspace.  Checked before any launch; n == 0 returns MUZ_OK; stream-ordered, no global state. */
+int muz_puct_search(const muz_net_w* w /*host*/, const muz_puct_cfg* cfg /*host*/, const float* root_logits,
+                    const float* root_value, const float* root_embedding, const uint32_t* legal_bits,
+                    const float* dirichlet, const float* gumbel, const int32_t* game_id, int32_t n, void* workspace,
+                    int64_t workspace_bytes, int32_t* action, float* action_weights, float* root_value_out,
+                    void* stream);
+
 /* ---- self-play (MuZero_det_MADN/game_agent.py:50-192) ----------------------------------------------
  * Trajectory buffers [n][T] per game, T = max_steps, mirroring play_batch_of_games_jitted's dict
  * (game_agent.py:158-169); obs is stored int8 (values 0..4, the reference keeps them as fp32). */
