@@ -115,10 +115,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     if (dirichlet_in) {
       dn = ok ? dirichlet_in[(size_t)g * A + ai] : 0.f;
     } else {
-      const float gm = ok ? gamma_sample(pa.dir_alpha, mix64(game_key(pa.seed ^ 0x5DEECE66Dull, gid, gturn) ^
-                                                             (unsigned long long)(a + 1)))
-                          : 0.f;
-      dn = gm / row_sum24(gm);
+      dn = row_softmax24(ok ? root_noise_log_gamma(pa.dir_alpha, pa.seed, gid, gturn, a) : 0.f, ok);
     }
     const float noisy = (1.f - pa.dir_frac) * pr + pa.dir_frac * dn;
     float lg = ok ? log_cr(fmaxf(noisy, kTinyF)) : -INFINITY;

@@ -1,6 +1,10 @@
 // Counter-based random numbers of the engine (splitmix64 finaliser over (seed, game, turn, ...)).
 // The reference draws with jax threefry, which is not restated: every stream here is documented in
-// include/muz.h and restated bit-exactly by the test oracles (oracle/selfplay.py, oracle/mctx_stochastic.py).
+// include/muz.h and restated by the test oracles.  The hashes and the uniforms are restated bit-exactly
+// (oracle/selfplay.py, oracle/mctx_stochastic.py, oracle/root_noise.py).  The root Dirichlet noise goes through libm
+// (log, cos, sqrt, exp), so its restatement (oracle/root_noise.py) agrees with the device to a few float32 ulps, not
+// bit for bit: tests/test_gpu_root_noise.py holds the device within 3x the float32 restatement's own distance from its
+// float64 run.
 #pragma once
 #include "common.hpp"
 
@@ -45,12 +49,17 @@ __device__ __forceinline__ float tiebreak_uniform(unsigned long long seed, int g
   return u24(h);
 }
 
-// Gamma(alpha) by Marsaglia-Tsang (alpha < 1 boosted through alpha + 1), uniforms from stream `key`.
+// log of a Gamma(alpha) draw by Marsaglia-Tsang (alpha < 1 boosted through alpha + 1), uniforms from stream `key`.
 // Bounded loops: acceptance is > 95 % per round, 32 rounds fail with probability < 1e-40.
-__device__ __forceinline__ float gamma_sample(float alpha, unsigned long long key) {
+// The draw stays in log space (as in jax.random.dirichlet): the boost U^(1/alpha) of a small alpha is far below the
+// smallest float32 (alpha 0.03: 7 % of the draws, and rows whose four draws are all 0), so the caller normalises a
+// row as the softmax of its log-gammas, which always has a largest term of 1 to divide by.
+__device__ __forceinline__ float log_gamma_sample(float alpha, unsigned long long key) {
+  // float32 operation by operation, as oracle/root_noise.py restates it (this header precedes nn.hpp's pin)
+#pragma clang fp contract(off)
   const float a = alpha < 1.f ? alpha + 1.f : alpha;
   const float d = a - 1.f / 3.f, c = 1.f / sqrtf(9.f * d);
-  float g = d;
+  float lg = logf(d);
   for (int it = 0; it < 32; ++it) {
     const float u1 = fmaxf(u24(mix64(key ^ (4ull * it + 1))), kTinyF);
     const float u2 = u24(mix64(key ^ (4ull * it + 2)));
@@ -60,12 +69,20 @@ __device__ __forceinline__ float gamma_sample(float alpha, unsigned long long ke
     v = v * v * v;
     const float u = fmaxf(u24(mix64(key ^ (4ull * it + 3))), kTinyF);
     if (logf(u) < 0.5f * x * x + d - d * v + d * logf(v)) {
-      g = d * v;
+      lg = logf(d * v);
       break;
     }
   }
-  if (alpha < 1.f) g *= powf(fmaxf(u24(mix64(key ^ 0xA5A5A5A5ull)), kTinyF), 1.f / alpha);
-  return g;
+  if (alpha < 1.f) lg += logf(fmaxf(u24(mix64(key ^ 0xA5A5A5A5ull)), kTinyF)) / alpha;
+  return lg;
+}
+
+// The root Dirichlet noise of the muzero_policy searches (k_stochastic_search, k_puct_search; muz_root_noise_diag
+// reads it out): the log of the Gamma(alpha) draw of action a of game gid at turn `turn`.  The noise is the softmax of
+// the row's log-gammas, which each root block takes in its own summation order.
+constexpr unsigned long long kRootNoiseStream = 0x5DEECE66Dull;
+__device__ __forceinline__ float root_noise_log_gamma(float alpha, unsigned long long seed, int gid, int turn, int a) {
+  return log_gamma_sample(alpha, mix64(game_key(seed ^ kRootNoiseStream, gid, turn) ^ (unsigned long long)(a + 1)));
 }
 
 // The evaluation agents' sampling (jax.random.categorical as argmax(logits + Gumbel)): the Gumbel draw of action a

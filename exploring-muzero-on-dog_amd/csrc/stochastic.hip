@@ -181,7 +181,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_stochastic_search(
     if (dirichlet_in) {
       dn = act_lane ? dirichlet_in[(size_t)g * A + a] : 0.f;
     } else {
-      const float gm = act_lane ? gamma_sample(sa.dir_alpha, mix64(game_key(sa.seed ^ 0x5DEECE66Dull, gid, gturn) ^ (unsigned long long)(a + 1))) : 0.f;
+      const float lgm = act_lane ? root_noise_log_gamma(sa.dir_alpha, sa.seed, gid, gturn, a) : -INFINITY;
+      const float lgx = row_max(lgm);
+      const float gm = act_lane ? expf(lgm - lgx) : 0.f;
       dn = gm / row_sum(gm);
     }
     const float noisy = (1.f - sa.dir_frac) * pr + sa.dir_frac * dn;

@@ -348,6 +348,8 @@ SIGNATURES = {
     "muz_stochastic_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
     "muz_stochastic_search": (ctypes.c_int, [ctypes.POINTER(MuzClassicNetW), ctypes.POINTER(MuzStochCfg), vp, vp, vp,
                                              vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "muz_root_noise_diag": (ctypes.c_int, [ctypes.c_uint64, ctypes.c_int32, vp, ctypes.c_float, ctypes.c_int32,
+                                           ctypes.c_int32, vp, vp, vp]),
     "muz_classic_selfplay_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32,
                                                               ctypes.POINTER(MuzStochCfg)]),
     "muz_classic_selfplay": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzClassicNetW),

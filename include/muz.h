@@ -593,6 +593,18 @@ int muz_stochastic_search(const muz_classic_net_w* w, const muz_stoch_cfg* cfg, 
                           void* workspace, int64_t workspace_bytes, int32_t* action, float* action_weights,
                           float* root_value_out, void* stream);
 
+/* Diagnostic readout of the root Dirichlet noise that muz_stochastic_search (num_actions 4) and muz_puct_search
+ * (num_actions 24) draw on the device when their `dirichlet` argument is NULL, through the helper both kernels call
+ * (csrc/rng.hpp root_noise_log_gamma) and each search's own row normalisation.  Its own contract: for row r < n,
+ * game = game_id ? game_id[r] : r, action a < num_actions: gamma [n][num_actions] = the Gamma(alpha) draw of
+ * (seed, game, turn, a) (exp of the log-gamma the kernels keep; it may underflow to 0 at small alpha), noise
+ * [n][num_actions] = the row's softmax of the log-gammas = the Dirichlet(alpha) sample the root prior is mixed with.
+ * A row depends on (seed, game, turn, alpha, num_actions) only, not on n or r.  Restated by oracle/root_noise.py.
+ * MUZ_E_UNSUPPORTED: num_actions not 4 or 24, alpha <= 0.  MUZ_E_INVALID: n < 0 or a null output.  Checked before any
+ * launch; n == 0 returns MUZ_OK and launches nothing; stream-ordered, no workspace, no global state. */
+int muz_root_noise_diag(uint64_t seed, int32_t turn, const int32_t* game_id /*nullable*/, float alpha,
+                        int32_t num_actions, int32_t n, float* gamma, float* noise, void* stream);
+
 /* Chance records of the stochastic self-play buffers (game_agent_stochastic.py:165-172). */
 typedef struct muz_traj_chance {
   int32_t* dice;      /* [n][T]     die of the turn (1..6) */

@@ -11,8 +11,9 @@
 //
 // Randomness: the die, the 1e-7 tie-break uniforms and the final categorical's Gumbel draws use the engine's
 // counter RNG (as the oracle restates it), so a trace can be compared with the oracle's; the root Dirichlet
-// noise (fraction 0.25, alpha 0.3 in the reference) is drawn here with Marsaglia-Tsang gamma samples from the
-// same counter hash -- parity-checked runs use fraction 0, as the oracle does.
+// noise (fraction 0.25, alpha 0.3 in the reference) is drawn here with Marsaglia-Tsang gamma samples on a stream
+// of this file's own (dirichlet_noise), NOT the engine's stream that oracle/root_noise.py restates -- so the
+// runs compared with the oracle's trace use fraction 0.
 #include "cpu_nets.hpp"
 
 namespace {
@@ -403,7 +404,10 @@ struct SSearch {
 };
 
 // Dirichlet(alpha) noise over the kAc root actions from the counter hash (Marsaglia-Tsang gamma; alpha < 1 via
-// the U^(1/alpha) boost): the CPU baseline's stand-in for the reference's jax.random.dirichlet
+// the U^(1/alpha) boost): the CPU baseline's stand-in for the reference's jax.random.dirichlet, for throughput
+// measurements only.  It is a sampler of the same distribution on its own stream (its own stream constant, one chained
+// counter per game, unbounded rounds, linear-space normalisation), not a restatement of the engine's draw
+// (csrc/rng.hpp root_noise_log_gamma, restated by oracle/root_noise.py); nothing compares the two.
 void dirichlet_noise(uint64_t seed, int gid, int turn, float alpha, float* out) {
   uint64_t ctr = mix64(seed ^ 0xD121C4E7ull ^ mix64(((uint64_t)(uint32_t)gid << 32) | (uint32_t)turn));
   auto uni = [&]() {

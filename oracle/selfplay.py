@@ -119,16 +119,22 @@ def die_uniform(seed, g, turn):
     return np.float32((h >> 40) * (1.0 / 16777216.0))
 
 
+def root_dirichlet(seed, gids, step, alpha=0.3, A=4):
+    """The engine's root Dirichlet noise of games `gids` at their step `step` (csrc/rng.hpp root_noise_log_gamma, keyed
+    by game number and the game's own step count): the float32 restatement of oracle/root_noise.py."""
+    from oracle import root_noise as RN
+    return RN.dirichlet(seed, gids, step, alpha, A)
+
+
 def play_batch_of_games_stochastic(params, root_fn, decision_fn, chance_fn, envs, num_simulations, max_depth,
                                    max_steps, temp, seed, dirichlet_fraction=0.0, time_budget=None):
-    """game_agent_stochastic.py:52-218 over a list of oracle classic envs.  The root Dirichlet noise is
-    only supported with dirichlet_fraction 0 here (the engine's Gamma sampler is not restated).  With
-    `time_budget` (seconds) the loop also stops once that much wall time has passed (bench.py's CPU sample)."""
+    """game_agent_stochastic.py:52-218 over a list of oracle classic envs.  With dirichlet_fraction > 0 every search
+    gets the engine's root noise of (seed, game, step), restated (root_dirichlet).  With `time_budget` (seconds) the
+    loop also stops once that much wall time has passed (bench.py's CPU sample)."""
     import time as _time
     _t0 = _time.perf_counter()
     from oracle import classic_madn as cm
     from oracle import mctx_stochastic as MS
-    assert dirichlet_fraction == 0.0
     n = len(envs)
     P = envs[0].num_players
     C = cm.num_channels(P)
@@ -160,11 +166,13 @@ def play_batch_of_games_stochastic(params, root_fn, decision_fn, chance_fn, envs
             gids = np.array([i for i, _ in search])
             gum = np.stack([gumbel_noise(seed ^ GUMBEL_STREAM, int(i), step, A=4) for i in gids])
             lg, v, e = root_fn(params, obs)
+            noise = (root_dirichlet(seed, gids, step) if dirichlet_fraction > 0.0
+                     else np.zeros((len(search), 4), np.float32))
             trace = {}
             act, w, rv, _ = MS.stochastic_muzero_policy(params, lg, v, e, decision_fn, chance_fn, num_simulations,
-                                                        invalid, np.zeros((len(search), 4), np.float32), gum,
-                                                        max_depth=max_depth, temperature=temp, seed=seed, turn=step,
-                                                        gids=gids, dirichlet_fraction=0.0, trace=trace)
+                                                        invalid, noise, gum, max_depth=max_depth, temperature=temp,
+                                                        seed=seed, turn=step, gids=gids,
+                                                        dirichlet_fraction=dirichlet_fraction, trace=trace)
             for k, (i, _) in enumerate(search):
                 env = envs[i]
                 t = buf["idx"][i]

@@ -94,6 +94,46 @@ def test_puct_search_logic_matches_mctx_restatement(cuda, P, S, D, qt, temp, fra
     assert excused <= 2
 
 
+@pytest.mark.parametrize("qt,frac,with_gids", [("min_max", 0.25, True), ("min_max", 1.0, False),
+                                               ("parent_and_siblings", 0.25, False),
+                                               ("parent_and_siblings", 1.0, True)])
+def test_puct_search_device_noise(cuda, qt, frac, with_gids):
+    """The root noise drawn inside k_puct_search (dirichlet=None): the restatement is fed the float32 restatement of
+    the device stream (oracle/root_noise.py) for the same (seed, game ids, turn), which pins the kernel's keying, its
+    row normalisation and the mixing; at dirichlet_fraction 1 the prior is the noise alone.  Excuses: the oracle's own
+    near-ties and the games with a Gamma draw whose float64 acceptance margin is below the threshold of
+    tests/_root_noise.py (left out)."""
+    from oracle import root_noise as RN
+    from tests import _root_noise as H
+    N, M = _mods()
+    P, S, D, temp = 2, 16, 8, 1.0
+    params, net, obs, valid, bits, (lg, v, e) = setup(P)
+    gum = np.random.default_rng(3).gumbel(size=(B, 24)).astype(np.float32)
+    gids = (7 * np.arange(B) + 3).astype(np.int32)[::-1].copy() if with_gids else np.arange(B, dtype=np.int32)
+    seed, turn = 4321, 9
+    pol, rv = M.muzero_policy(net, lg, v, e, bits, S, D, temp, qtransform=qt, dirichlet_fraction=frac, dirichlet=None,
+                              gumbel=torch.from_numpy(gum), seed=seed, turn=turn,
+                              game_id=torch.from_numpy(gids) if with_gids else None)
+    r32 = RN.root_noise(seed, gids, turn, 0.3, 24, np.float32)
+    r64 = RN.root_noise(seed, gids, turn, 0.3, 24, np.float64)
+    ok = ~(r64["margin"] < H.threshold([(r32, r64)])).any(1)
+    assert (~ok).sum() <= H.MAX_EXCUSED * B
+    trace = {}
+    a, w, orv, _ = PZ.muzero_policy(params, lg.cpu().numpy(), v.cpu().numpy(), e.cpu().numpy(),
+                                    gpu_recurrent_fn(N, net), S, ~valid, r32["noise"], gum, max_depth=D,
+                                    temperature=temp, qtransform=qt, dirichlet_fraction=frac, seed=seed, turn=turn,
+                                    gids=gids, trace=trace)
+    torch.cuda.synchronize()
+    ga, gw, grv = pol.action.cpu().numpy(), pol.action_weights.cpu().numpy(), rv.cpu().numpy()
+    label = f"puct search device noise P{P} S{S} D{D} {qt} f{frac} game_id {'given' if with_gids else 'none'}"
+    search_parity(label, ga[ok], gw[ok], grv[ok], a[ok], w[ok], orv[ok], trace["margin"][ok], gain=None)
+    assert valid[np.arange(B), ga].all(), "search picked an invalid root action"
+    excused = int((ga[ok] != a[ok]).sum())
+    log(f"{label}: games excused by the noise's acceptance margin {int((~ok).sum())} of {B}, by an oracle near-tie "
+        f"{excused} (at most 2 allowed)")
+    assert excused <= 2
+
+
 def test_puct_device_rng_is_deterministic_and_valid(cuda):
     N, M = _mods()
     params, net, obs, valid, bits, (lg, v, e) = setup(2)

@@ -2,9 +2,10 @@
 game_agent_stochastic.py (GPU).
 
 The oracle loop is driven by the GPU network kernels and the same counter RNG (die uniforms, tie-break
-uniforms, final Gumbel draws); the root Dirichlet fraction is 0 on both sides (the engine's Gamma
-sampler is not restated), so everything else -- dice, env transitions, compaction, search, records --
-is compared exactly."""
+uniforms, final Gumbel draws), so dice, env transitions, compaction, search and records are compared
+exactly.  The root Dirichlet noise is drawn inside the search kernel; with dirichlet_fraction > 0 the oracle
+is fed the float32 restatement of that stream (oracle/root_noise.py) per (game, step), which together with
+test_classic_stream_equals_batch pins the stream's key_game / key_turn keying."""
 import numpy as np
 import pytest
 import torch
@@ -37,19 +38,38 @@ def gpu_fns(S, net):
     return root, dec, cha
 
 
-@pytest.mark.parametrize("n,Ssim,D,T,temp", [(12, 8, 6, 120, 1.0), (6, 16, 10, 90, 0.6)])
-def test_classic_selfplay_matches_oracle(cuda, n, Ssim, D, T, temp):
+@pytest.mark.parametrize("n,Ssim,D,T,temp,frac", [
+    pytest.param(12, 8, 6, 120, 1.0, 0.0, id="12-8-6-120-1.0"), pytest.param(6, 16, 10, 90, 0.6, 0.0, id="6-16-10-90-0.6"),
+    pytest.param(12, 8, 6, 120, 1.0, 0.25, id="12-8-6-120-1.0-dirichlet0.25")])
+def test_classic_selfplay_matches_oracle(cuda, n, Ssim, D, T, temp, frac):
+    """frac > 0: a turn whose root noise has a Gamma draw with a float64 acceptance margin below the threshold of
+    tests/_root_noise.py (over this game set's draws; at most 1 % of the searches) may differ wholesale: it is handed
+    to selfplay_parity as a near-tie (margin 0) and counted."""
     GS, S = _mods()
     C = cm.num_channels(4)
     params = CN.init_params(C, seed=13, randomize_affine=True)
     net = S.DeviceClassicNet(params, C)
     eng = GS.StochasticSelfPlayEngine(net, n, max_steps=T, num_simulations=Ssim, max_depth=D)
     seed = 4242
-    buf = {k: v.cpu().numpy() for k, v in eng.play(seed, temp, dirichlet_fraction=0.0).items()}
+    buf = {k: v.cpu().numpy() for k, v in eng.play(seed, temp, dirichlet_fraction=frac).items()}
     envs = [cm.env_reset(num_players=4, **cm.SELFPLAY_RULES) for _ in range(n)]
     root, dec, cha = gpu_fns(S, net)
-    ref, steps = OS.play_batch_of_games_stochastic(params, root, dec, cha, envs, Ssim, D, T, temp, seed)
-    diverged = selfplay_parity(f"classic self-play n{n} S{Ssim} D{D} T{temp}", buf, ref,
+    ref, steps = OS.play_batch_of_games_stochastic(params, root, dec, cha, envs, Ssim, D, T, temp, seed,
+                                                   dirichlet_fraction=frac)
+    label = f"classic self-play n{n} S{Ssim} D{D} T{temp}"
+    if frac > 0.0:
+        from oracle import root_noise as RN
+        from tests import _root_noise as H
+        from tests._parity import log
+        gi, ti = np.nonzero(ref["mask"] > 0)           # the searches: (game, the game's own step)
+        r32 = RN.root_noise(seed, gi, ti, 0.3, 4, np.float32)
+        r64 = RN.root_noise(seed, gi, ti, 0.3, 4, np.float64)
+        ex = (r64["margin"] < H.threshold([(r32, r64)])).any(1)
+        assert ex.sum() <= H.MAX_EXCUSED * len(gi)
+        ref["margin"][gi[ex], ti[ex]] = 0.0
+        label += f" dirichlet {frac}"
+        log(f"{label}: searches excused by the noise's acceptance margin {int(ex.sum())} of {len(gi)}")
+    diverged = selfplay_parity(label, buf, ref,
                                ("act", "rew", "player", "team", "discount", "mask", "dice", "obs", "dice_dist"))
     if not diverged:
         assert eng.last_turns == steps

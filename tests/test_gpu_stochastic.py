@@ -4,8 +4,10 @@
   (atol 1e-5 on logits / values / rewards / discounts, 2e-5 on the min-max normalised 256-d states,
   the tolerances of tests/test_gpu_nets.py);
 * search logic: the oracle search (oracle/mctx_stochastic.py) is driven by the GPU's own recurrent
-  kernels, so both trees see identical network outputs; root noise and the final Gumbel draws are
-  explicit inputs on both sides, the tie-break uniforms come from the same counter RNG.
+  kernels, so both trees see identical network outputs; the final Gumbel draws are explicit inputs on both
+  sides, the tie-break uniforms come from the same counter RNG; the root noise is an explicit input on both
+  sides (test_stochastic_search_logic) or drawn inside the kernel and restated for the oracle
+  (test_stochastic_search_device_noise, oracle/root_noise.py).
 Parity vs mctx itself is unpinned (mctx is not vendored in the reference)."""
 import numpy as np
 import pytest
@@ -124,9 +126,56 @@ def test_stochastic_search_logic(cuda, Ssim, D, temp):
     assert np.allclose(gw.sum(1), 1.0, atol=1e-6)
 
 
+@pytest.mark.parametrize("permuted", [False, True], ids=["game_id_none", "game_id_permuted"])
+@pytest.mark.parametrize("Ssim,D", [(16, 8), (8, 3)])
+def test_stochastic_search_device_noise(cuda, Ssim, D, permuted):
+    """The root noise drawn inside k_stochastic_search (dirichlet=None): the oracle search is fed the float32
+    restatement of the device stream (oracle/root_noise.py) for the same (seed, game ids, turn), which pins the
+    kernel's keying, row normalisation and mixing.  Excuses: the oracle's own near-ties, as everywhere, and the games
+    with a Gamma draw whose float64 acceptance margin is below the threshold of tests/_root_noise.py (left out)."""
+    from oracle import root_noise as RN
+    from tests import _root_noise as H
+    from tests._parity import log
+    S = _S()
+    C = cm.num_channels(4)
+    params = CN.init_params(C, seed=9, randomize_affine=True)
+    net = S.DeviceClassicNet(params, C)
+    obs, envs = random_classic_states(48, 4)
+    valid = np.stack([cm.valid_action(e) for e in envs])
+    keep = valid.any(1)
+    obs, valid = obs[keep], valid[keep]
+    B = obs.shape[0]
+    bits = (valid.astype(np.int64) << np.arange(4)).sum(1).astype(np.int32)
+    lg, v, e = S.root_inference_fn(net, torch.from_numpy(obs).cuda())
+    rng = np.random.default_rng(3)
+    gumbel = rng.gumbel(size=(B, 4)).astype(np.float32)
+    gids = (rng.permutation(B) + 1000).astype(np.int32) if permuted else np.arange(B, dtype=np.int32)
+    seed, turn = 1234, 7
+    act, w, rv = S.stochastic_muzero_policy(net, lg, v, e, torch.from_numpy(bits), Ssim, D, 1.0, seed=seed, turn=turn,
+                                            dirichlet=None, gumbel=torch.from_numpy(gumbel),
+                                            game_id=torch.from_numpy(gids) if permuted else None)
+    r32 = RN.root_noise(seed, gids, turn, 0.3, 4, np.float32)
+    r64 = RN.root_noise(seed, gids, turn, 0.3, 4, np.float64)
+    ok = ~(r64["margin"] < H.threshold([(r32, r64)])).any(1)
+    assert (~ok).sum() <= H.MAX_EXCUSED * B
+    dec, cha = gpu_fns(S, net)
+    trace = {}
+    oa, ow, orv, _ = MS.stochastic_muzero_policy(params, lg.cpu().numpy(), v.cpu().numpy(), e.cpu().numpy(), dec, cha,
+                                                 Ssim, ~valid, r32["noise"], gumbel, max_depth=D, temperature=1.0,
+                                                 seed=seed, turn=turn, gids=gids, trace=trace)
+    torch.cuda.synchronize()
+    ga, gw, grv = act.cpu().numpy(), w.cpu().numpy(), rv.cpu().numpy()
+    label = f"stochastic search device noise S{Ssim} D{D} game_id {'permuted' if permuted else 'none'}"
+    search_parity(label, ga[ok], gw[ok], grv[ok], oa[ok], ow[ok], orv[ok], trace["margin"][ok])
+    log(f"{label}: games excused by the noise's acceptance margin {int((~ok).sum())} of {B}, by an oracle near-tie "
+        f"{int((ga[ok] != oa[ok]).sum())}")
+    assert valid[np.arange(B), ga].all(), "search picked an illegal pin"
+
+
 def test_stochastic_search_device_rng(cuda):
-    """Device Dirichlet (Gamma sampler) and Gumbel streams: legal actions, proper visit distributions,
-    deterministic for a fixed seed, different for another."""
+    """Device Dirichlet and Gumbel streams through the observation-level entry point: legal actions, proper visit
+    distributions, deterministic for a fixed seed, different for another.  (What the Dirichlet stream draws is pinned
+    by test_stochastic_search_device_noise and tests/test_gpu_root_noise.py.)"""
     S = _S()
     C = cm.num_channels(4)
     net = S.DeviceClassicNet(CN.init_params(C, seed=1), C)
