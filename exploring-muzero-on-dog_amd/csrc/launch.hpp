@@ -14,6 +14,19 @@ static inline int check_search_limits(int num_simulations, int max_depth) {
   const bool ok = num_simulations >= 1 && num_simulations <= kMaxSims && max_depth >= 1 && max_depth <= kMaxDepth;
   return ok ? MUZ_OK : MUZ_E_UNSUPPORTED;
 }
+// What muz_gumbel_search, muz_puct_search and muz_stochastic_search check once the network and the policy's own
+// settings are accepted: the limits (unsupported), then the buffers every search takes and the workspace size (invalid;
+// need: the search's workspace bytes for (n, num_simulations)).
+static inline int check_search_call(int num_simulations, int max_depth, int n, const void* root_logits,
+                                    const void* root_value, const void* root_embedding, const void* legal_bits,
+                                    const void* workspace, int64_t workspace_bytes, int64_t (*need)(int, int),
+                                    const void* action, const void* action_weights, const void* root_value_out) {
+  if (check_search_limits(num_simulations, max_depth)) return MUZ_E_UNSUPPORTED;
+  MUZ_HOST_CHECK(n >= 0 && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
+                 action_weights && root_value_out);
+  MUZ_HOST_CHECK(workspace_bytes >= need(n, num_simulations));
+  return MUZ_OK;
+}
 
 struct SearchArgs {
   int S, D, max_considered;

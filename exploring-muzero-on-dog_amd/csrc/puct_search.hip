@@ -1,9 +1,10 @@
 // Batched PUCT MuZero search for det-MADN (mctx 0.0.6 muzero_policy: the call run_muzero_mcts keeps commented beside
 // the Gumbel one, MuZero_det_MADN/muzero_deterministic_madn.py:685-697) as ONE persistent kernel per search.
 //
-// The geometry and the expansion are k_gumbel_search's (search.hip): a workgroup owns 16 games for the whole search,
-// 32 lanes per game, lane a holds child a; root children in registers, node scalars and the path in LDS, children
-// arrays and node embeddings in the workspace; Dyn4 + Pred4 on MFMA over the 16-row tile.  What differs:
+// The geometry and the expansion are k_gumbel_search's (search.hip), the simulation body (walk, expansion and backup
+// commits) the one both take from tree.hpp: a workgroup owns 16 games for the whole search, 32 lanes per game, lane a
+// holds child a; root children in registers, node scalars and the path in LDS, children arrays and node embeddings in
+// the workspace; Dyn4 + Pred4 on MFMA over the 16-row tile.  What differs:
 //   root    -- Dirichlet noise mixed into softmax(root_logits), log, mask (policies.py muzero_policy);
 //   select  -- muzero_action_selection at every level: qtransform + sqrt(N) pb_c(N) softmax(prior) / (n + 1) + 1e-7 U,
 //              the root mask at depth 0;
@@ -15,19 +16,7 @@
 
 namespace muz {
 
-#ifndef MUZ_LATE_HEADS
-#define MUZ_LATE_HEADS 0
-#endif
-#ifndef MUZ_BACKUP_CHUNK
-#define MUZ_BACKUP_CHUNK kRowLanes
-#endif
-
 namespace {
-
-constexpr bool kLateHeads = MUZ_LATE_HEADS != 0;   // as in search.hip
-constexpr int kAPad = 32;                          // children arrays padded to 32 actions
-constexpr int kBackupChunk = MUZ_BACKUP_CHUNK;
-using TreeWs = NarrowTree<kAPad>;
 
 // ---- the tree arithmetic, bit for bit like the NumPy restatement (tests/_mctx_muzero.py) ---------------------------
 // As in search.hip: no fma contraction, sums over the 24 actions in row_sum24's order, exp and log correctly rounded
@@ -67,15 +56,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
   // tree arithmetic exactly as written; the networks (nn.hpp) keep their own contraction
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
-  __shared__ int s_visits[kRows][kMaxNodes];
-  __shared__ float s_val[kRows][kMaxNodes];
-  __shared__ int p_node[kRows][kMaxDepth];
-  __shared__ int p_act[kRows][kMaxDepth];
-  __shared__ int p_cvis[kRows][kMaxDepth];
-  __shared__ float p_rew[kRows][kMaxDepth];
-  __shared__ float p_disc[kRows][kMaxDepth];
-  __shared__ int s_act[kRows], s_parent[kRows], s_next[kRows], s_depth[kRows];
-  __shared__ float s_rootv[kRows];
+  __shared__ SearchLds L;
   __shared__ float s_pbtab[kMaxNodes + 1];   // sqrt(N) * pb_c(N) for a node's visit count N = 0..S+1
 
   if ((int)blockIdx.x * kRows >= n) return;
@@ -125,25 +106,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     for (int c = a; c < LAT; c += kRowLanes) e0[c] = root_emb[(size_t)g * LAT + c];
     if (a == 0) {
       const float v = root_value[g];
-      s_visits[row][0] = 1;
-      s_val[row][0] = v;
+      L.visits[row][0] = 1;
+      L.val[row][0] = v;
     }
   }
   __syncthreads();
-
-  // one node's children for this lane
-  auto load_kid = [&](int node) {
-    Kid k;
-    const size_t e = T.ca(g, node, ai);
-    k.ok = ok;
-    k.prior = tree_ld(T.prior() + e);
-    k.value = tree_ld(T.value() + e);
-    k.reward = tree_ld(T.reward() + e);
-    k.disc = tree_ld(T.disc() + e);
-    k.visits = ok ? tree_ld(T.visits() + e) : 0;
-    k.index = tree_ld(T.index() + e);
-    return k;
-  };
 
   st_begin();
   Pf pf;   // first k-blocks of the next dense layer (crosses the select / expand phases)
@@ -156,101 +123,34 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     int dact = 0;
     // ---------------- simulate (search.py simulate): walk from the root
     if (valid) {
-      int node = 0, depth = 0, act = 0, nxt = -1;
-      while (true) {
-        const Kid k = depth == 0 ? rk : load_kid(node);
+      const WalkEnd w = walk(T, L, rk, pa.D, [&](const Kid& k, int node, int depth) -> float {
         // muzero_action_selection: value_score + policy_score + 1e-7 U, masked at the root
-        const float vs = value_score<QT>(k, s_val[row][node], pa);
-        const float ps = s_pbtab[s_visits[row][node]] * k.prior / (float)(k.visits + 1);
+        const float vs = value_score<QT>(k, L.val[row][node], pa);
+        const float ps = s_pbtab[L.visits[row][node]] * k.prior / (float)(k.visits + 1);
         const float tb = tiebreak_uniform(pa.seed, gid, gturn, sim, depth, ai);
-        float sc = vs + ps + 1e-7f * tb;
-        if (!ok || (depth == 0 && inv)) sc = -INFINITY;
-        int bi = a;
-        row_argmax(sc, bi);
-        const int child = __shfl(k.index, bi, kRowLanes);
-        if (a == bi) {
-          p_node[row][depth] = node;
-          p_act[row][depth] = bi;
-          p_rew[row][depth] = k.reward;
-          p_disc[row][depth] = k.disc;
-          p_cvis[row][depth] = k.visits;
-        }
-        act = bi;
-        nxt = child;
-        ++depth;
-        if (child == -1 || depth >= pa.D) break;
-        node = child;
-      }
+        return (!ok || (depth == 0 && inv)) ? -INFINITY : vs + ps + 1e-7f * tb;
+      });
       // expand's inputs (parent embedding, FiLM rows of the action): issued by the game's own lanes now
-      din = dyn_load(wl->dyn, A, T.e(g, node), act);
-      dact = act;
-      if (a == 0) {
-        s_parent[row] = node;
-        s_act[row] = act;
-        s_next[row] = (nxt == -1) ? sim + 1 : nxt;
-        s_depth[row] = depth;
-      }
+      din = dyn_load(wl->dyn, A, T.e(g, w.node), w.act);
+      dact = w.act;
+      if (a == 0) L.hand_off(row, w, sim);
     } else {
       din = dyn_load(wl->dyn, A, nullptr, 0);
-      if (a == 0) s_act[row] = 0;
+      if (a == 0) L.act[row] = 0;
     }
     ST(ST_SEL);
     SYNC();
     // ---------------- expand (search.py expand): recurrent_fn on the 16 parents, as k_gumbel_search does
-    const int nx = s_next[row];
+    const int nx = L.next[row];
     dyn16<NT256, true, kLateHeads>(wl->dyn, A, din, dact, ar, pf, &wl->pred.rb[0].d0, LAT, LAT, &wl->pred.ln0,
                                    valid ? T.e(g, nx) : nullptr);
     pred16<NT256, true, kLateHeads, kSplitkLogits>(wl->pred, A, ar.T, ar, pf, &wl->dyn.d3, LAT, LAT, &wl->dyn, dact);
     if (valid) {
-      const bool fresh = nx == sim + 1;
-      const float pp = row_softmax24(ar.U[row * LD + ai], ok);   // the new node's prior probabilities
-      if (ok) {
-        const size_t nb = T.ca(g, nx, a);
-        tree_st(T.prior() + nb, pp);
-        if (fresh) {
-          tree_st(T.index() + nb, -1);
-          tree_st(T.visits() + nb, 0);
-          tree_st(T.value() + nb, 0.f);
-          tree_st(T.reward() + nb, 0.f);
-          tree_st(T.disc() + nb, 0.f);
-        }
-      }
-      const int par = s_parent[row], pact = s_act[row];
-      if (par == 0 && a == pact) {   // a root edge: registers
-        rk.index = nx;
-        rk.reward = ar.v1[row];
-        rk.disc = ar.v2[row];
-      }
+      // the new node keeps its prior probabilities
       const float v = ar.v0[row], rw = ar.v1[row], dc = ar.v2[row];
-      if (a == 0) {
-        if (par != 0) {
-          const size_t eb = T.ca(g, par, pact);
-          tree_st(T.index() + eb, nx);
-          tree_st(T.reward() + eb, rw);
-          tree_st(T.disc() + eb, dc);
-        }
-        s_val[row][nx] = v;
-        s_visits[row][nx] = fresh ? 1 : s_visits[row][nx] + 1;
-      }
-      // ---------------- backward (search.py backward) along the recorded path, as k_gumbel_search does
-      const PathRow path{p_node[row], p_act[row], p_cvis[row], p_rew[row], p_disc[row], s_visits[row], s_val[row]};
-      backup_lanes<kBackupChunk>(path, a, s_depth[row], v, rw, dc,
-                                 [&](int l, int parent, int pa_, int cvis, float, float, float child_v) {
-                                   if (l > 0) {
-                                     const size_t ei = T.ca(g, parent, pa_);
-                                     tree_st(T.value() + ei, child_v);
-                                     tree_st(T.visits() + ei, cvis + 1);
-                                   } else {
-                                     s_rootv[row] = child_v;
-                                   }
-                                 });
-      // the root edge of this path (level 0): its lane takes the value lane 0 just backed up
-      // (same wave: LDS operations of one wave complete in order)
-      __builtin_amdgcn_wave_barrier();
-      if (a == p_act[row][0]) {
-        rk.value = s_rootv[row];
-        rk.visits += 1;
-      }
+      commit_expansion(T, L, rk, sim, row_softmax24(ar.U[row * LD + ai], ok), v, rw, dc);
+      // ---------------- backward (search.py backward) along the recorded path
+      commit_backup(T, L, rk, v, rw, dc);
     }
     ST(ST_TREE);
     SYNC();
@@ -274,7 +174,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     if (ok) out_weights[(size_t)g * A + a] = w;
     if (a == 0) {
       out_action[g] = bi;
-      out_value[g] = s_val[row][0];
+      out_value[g] = L.val[row][0];
     }
   }
 }
@@ -309,16 +209,15 @@ int muz_puct_search(const muz_net_w* w, const muz_puct_cfg* cfg, const float* ro
                     int32_t* action, float* action_weights, float* root_value_out, void* stream) {
   if (!w || !cfg) return MUZ_E_INVALID;
   if (w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
-  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
   if (cfg->qtransform != MUZ_QT_MIN_MAX && cfg->qtransform != MUZ_QT_PARENT_SIBLINGS) return MUZ_E_UNSUPPORTED;
   // (written so that a NaN is refused too)
   if (!(cfg->max_value > cfg->min_value)) return MUZ_E_UNSUPPORTED;
   if (!(cfg->dirichlet_fraction >= 0.f && cfg->dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
   if (!(cfg->dirichlet_alpha > 0.f) || !(cfg->pb_c_base > 0.f) || !(cfg->temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
-  MUZ_HOST_CHECK(n >= 0 && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
-                 action_weights && root_value_out);
-  MUZ_HOST_CHECK(workspace_bytes >= search_workspace_bytes(n, cfg->num_simulations));
-  if (n == 0) return MUZ_OK;
+  const int rc = check_search_call(cfg->num_simulations, cfg->max_depth, n, root_logits, root_value, root_embedding,
+                                   legal_bits, workspace, workspace_bytes, search_workspace_bytes, action,
+                                   action_weights, root_value_out);
+  if (rc || n == 0) return rc;
   return launch_puct_search(*w, make_puct_args(*cfg), root_logits, root_value, root_embedding, legal_bits, dirichlet,
                             gumbel, game_id, n, workspace, action, action_weights, root_value_out, (hipStream_t)stream);
 }

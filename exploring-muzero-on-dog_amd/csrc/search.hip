@@ -34,21 +34,7 @@ __device__ unsigned long long g_muz_stamps[8];
 // them measured within noise on MI355X (B=4096 S=50: +-1 %), so they stay.  A static s_setprio 1 for
 // waves 4-7 also measured within noise (profiles/r1e_prio_ab.log).
 
-// Dyn4's reward / discount trunk inside Pred4's Dense_1 phase (nn.hpp pred16 LATE_HEADS)
-#ifndef MUZ_LATE_HEADS
-#define MUZ_LATE_HEADS 0
-#endif
-constexpr bool kLateHeads = MUZ_LATE_HEADS != 0;
-
-constexpr int kAPad = 32;                  // children arrays padded to 32 actions
-// levels per backup chunk (one per lane; backup_lanes, tree.hpp).  A smaller value (make EXTRA=-DMUZ_BACKUP_CHUNK=4)
-// runs the chunked path of max_depth > 32 at ordinary depths; no committed test builds that variant
-#ifndef MUZ_BACKUP_CHUNK
-#define MUZ_BACKUP_CHUNK kRowLanes
-#endif
-constexpr int kBackupChunk = MUZ_BACKUP_CHUNK;
-
-using TreeWs = NarrowTree<kAPad>;
+// (kLateHeads, kBackupChunk and the det-MADN tree TreeWs: tree.hpp)
 
 // ---- the tree arithmetic, bit for bit like the NumPy restatement (oracle/mctx_gumbel.py) -------------------
 // With identical network outputs on both sides the search's floats then agree exactly (tests/_parity.py):
@@ -91,16 +77,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   // tree arithmetic exactly as written (see row_sum24); the networks (nn.hpp) keep their own contraction
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
-  __shared__ int s_visits[kRows][kMaxNodes];
+  __shared__ SearchLds L;
   __shared__ float s_raw[kRows][kMaxNodes];
-  __shared__ float s_val[kRows][kMaxNodes];
-  __shared__ int p_node[kRows][kMaxDepth];
-  __shared__ int p_act[kRows][kMaxDepth];
-  __shared__ int p_cvis[kRows][kMaxDepth];
-  __shared__ float p_rew[kRows][kMaxDepth];
-  __shared__ float p_disc[kRows][kMaxDepth];
-  __shared__ int s_act[kRows], s_parent[kRows], s_next[kRows], s_depth[kRows];
-  __shared__ float s_rootv[kRows];
 
   if (n_dev) n = *n_dev;
   if ((int)blockIdx.x * kRows >= n) return;
@@ -145,26 +123,12 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     ncons = min(sa.max_considered, __popc(lb & ((1u << A) - 1u)));
     if (a == 0) {
       const float v = root_value[g];
-      s_visits[row][0] = 1;
+      L.visits[row][0] = 1;
       s_raw[row][0] = v;
-      s_val[row][0] = v;
+      L.val[row][0] = v;
     }
   }
   __syncthreads();
-
-  // one node's children for this lane
-  auto load_kid = [&](int node) {
-    Kid k;
-    const size_t e = T.ca(g, node, ai);
-    k.ok = ok;
-    k.prior = tree_ld(T.prior() + e);
-    k.value = tree_ld(T.value() + e);
-    k.reward = tree_ld(T.reward() + e);
-    k.disc = tree_ld(T.disc() + e);
-    k.visits = ok ? tree_ld(T.visits() + e) : 0;
-    k.index = tree_ld(T.index() + e);
-    return k;
-  };
 
   st_begin();
   Pf pf;   // first k-blocks of the next dense layer (crosses the select / expand phases)
@@ -180,55 +144,31 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     int dact = 0;
     // ---------------- simulate (search.py simulate): walk from the root
     if (valid) {
-      int node = 0, depth = 0, act = 0, nxt = -1;
-      while (true) {
-        const Kid k = depth == 0 ? rk : load_kid(node);
+      const WalkEnd w = walk(T, L, rk, sa.D, [&](const Kid& k, int node, int depth) -> float {
         int sumv;
         float pmax;
         const float cq = completed_q(k, s_raw[row][node], sa, sumv, pmax);
-        float sc;
         if (depth == 0) {
           // gumbel_muzero_root_action_selection: score_considered + masked_argmax
           const int cv = considered_visit(ncons, sa.S, sumv);
           const float s = fmaxf(-1e9f, gum + (k.prior - pmax) + cq) + (k.visits == cv ? 0.f : -INFINITY);
-          sc = (!ok || ((lb >> a) & 1u) == 0u) ? -INFINITY : s;
-        } else {
-          // gumbel_muzero_interior_action_selection: softmax(prior + cq) - N / (1 + sum N)
-          const float z = k.prior + cq;
-          const float zm = row_max(ok ? z : -INFINITY);
-          const float ez = ok ? exp_cr(z - zm) : 0.f;
-          const float zs = row_sum24(ez);
-          sc = ok ? (ez / zs - (float)k.visits / (float)(1 + sumv)) : -INFINITY;
+          return (!ok || ((lb >> a) & 1u) == 0u) ? -INFINITY : s;
         }
-        int bi = a;
-        row_argmax(sc, bi);
-        const int child = __shfl(k.index, bi, kRowLanes);
-        if (a == bi) {
-          p_node[row][depth] = node;
-          p_act[row][depth] = bi;
-          p_rew[row][depth] = k.reward;
-          p_disc[row][depth] = k.disc;
-          p_cvis[row][depth] = k.visits;
-        }
-        act = bi;
-        nxt = child;
-        ++depth;
-        if (child == -1 || depth >= sa.D) break;
-        node = child;
-      }
+        // gumbel_muzero_interior_action_selection: softmax(prior + cq) - N / (1 + sum N)
+        const float z = k.prior + cq;
+        const float zm = row_max(ok ? z : -INFINITY);
+        const float ez = ok ? exp_cr(z - zm) : 0.f;
+        const float zs = row_sum24(ez);
+        return ok ? (ez / zs - (float)k.visits / (float)(1 + sumv)) : -INFINITY;
+      });
       // expand's inputs (parent embedding, FiLM rows of the action): issued by the game's own lanes now,
       // they land while the other games finish their walks
-      din = dyn_load(wl->dyn, A, T.e(g, node), act);
-      dact = act;
-      if (a == 0) {
-        s_parent[row] = node;
-        s_act[row] = act;
-        s_next[row] = (nxt == -1) ? sim + 1 : nxt;
-        s_depth[row] = depth;
-      }
+      din = dyn_load(wl->dyn, A, T.e(g, w.node), w.act);
+      dact = w.act;
+      if (a == 0) L.hand_off(row, w, sim);
     } else {
       din = dyn_load(wl->dyn, A, nullptr, 0);
-      if (a == 0) s_act[row] = 0;
+      if (a == 0) L.act[row] = 0;
     }
     ST(ST_SEL);
     // (Dyn4's first pass -- LayerNorm_0 + FiLM of the parent latent -- only reads this row's own registers
@@ -238,7 +178,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     // ---------------- expand (search.py expand): recurrent_fn on the 16 parents
     // the new node's embedding goes to the tree and Pred4's LayerNorm_0 into ar.X straight from Dyn4's
     // min-max pass (registers), so Pred4 starts with its first ResBlock
-    const int nx = s_next[row];
+    const int nx = L.next[row];
     dyn16<NT256, true, kLateHeads>(wl->dyn, A, din, dact, ar, pf, &wl->pred.rb[0].d0, LAT, LAT, &wl->pred.ln0,
                                    valid ? T.e(g, nx) : nullptr);
     MUZ_STAMP(3);   // dynamics
@@ -246,56 +186,12 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     pred16<NT256, true, kLateHeads, kSplitkLogits>(wl->pred, A, ar.T, ar, pf, &wl->dyn.d3, LAT, LAT, &wl->dyn, dact);
     MUZ_STAMP(5);   // prediction
     if (valid) {
-      const bool fresh = nx == sim + 1;
-      if (ok) {
-        const size_t nb = T.ca(g, nx, a);
-        tree_st(T.prior() + nb, ar.U[row * LD + a]);
-        if (fresh) {
-          tree_st(T.index() + nb, -1);
-          tree_st(T.visits() + nb, 0);
-          tree_st(T.value() + nb, 0.f);
-          tree_st(T.reward() + nb, 0.f);
-          tree_st(T.disc() + nb, 0.f);
-        }
-      }
-      const int par = s_parent[row], pa = s_act[row];
-      if (par == 0 && a == pa) {   // a root edge: registers
-        rk.index = nx;
-        rk.reward = ar.v1[row];
-        rk.disc = ar.v2[row];
-      }
+      // the new node keeps its prior logits
       const float v = ar.v0[row], rw = ar.v1[row], dc = ar.v2[row];
-      if (a == 0) {
-        if (par != 0) {
-          const size_t eb = T.ca(g, par, pa);
-          tree_st(T.index() + eb, nx);
-          tree_st(T.reward() + eb, rw);
-          tree_st(T.disc() + eb, dc);
-        }
-        s_raw[row][nx] = v;
-        s_val[row][nx] = v;
-        s_visits[row][nx] = fresh ? 1 : s_visits[row][nx] + 1;
-      }
-      // ---------------- backward (search.py backward) along the recorded path: an interior edge's new value and
-      // visit count go to the tree, the root edge's value (level 0: registers) to s_rootv
-      const PathRow path{p_node[row], p_act[row], p_cvis[row], p_rew[row], p_disc[row], s_visits[row], s_val[row]};
-      backup_lanes<kBackupChunk>(path, a, s_depth[row], v, rw, dc,
-                                 [&](int l, int parent, int pact, int cvis, float, float, float child_v) {
-                                   if (l > 0) {
-                                     const size_t ei = T.ca(g, parent, pact);
-                                     tree_st(T.value() + ei, child_v);
-                                     tree_st(T.visits() + ei, cvis + 1);
-                                   } else {
-                                     s_rootv[row] = child_v;
-                                   }
-                                 });
-      // the root edge of this path (level 0): its lane takes the value lane 0 just backed up
-      // (same wave: LDS operations of one wave complete in order)
-      __builtin_amdgcn_wave_barrier();
-      if (a == p_act[row][0]) {
-        rk.value = s_rootv[row];
-        rk.visits += 1;
-      }
+      commit_expansion(T, L, rk, sim, ar.U[row * LD + ai], v, rw, dc);
+      if (a == 0) s_raw[row][nx] = v;
+      // ---------------- backward (search.py backward) along the recorded path
+      commit_backup(T, L, rk, v, rw, dc);
     }
     ST(ST_TREE);
     // (The next walk of row r reads only what row r's own lanes -- one wave -- wrote here: this barrier is
@@ -331,7 +227,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     if (ok) out_weights[(size_t)g * A + a] = ez / zs;
     if (a == 0) {
       out_action[g] = bi;
-      out_value[g] = s_val[row][0];
+      out_value[g] = L.val[row][0];
     }
   }
 }
@@ -365,12 +261,11 @@ int muz_gumbel_search(const muz_net_w* w, const muz_search_cfg* cfg, const float
                       float* action_weights, float* root_value_out, void* stream) {
   if (!w || !cfg) return MUZ_E_INVALID;
   if (w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
-  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
   if (cfg->max_num_considered < 1) return MUZ_E_UNSUPPORTED;
-  MUZ_HOST_CHECK(n >= 0 && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
-                 action_weights && root_value_out);
-  MUZ_HOST_CHECK(workspace_bytes >= search_workspace_bytes(n, cfg->num_simulations));
-  if (n == 0) return MUZ_OK;
+  const int rc = check_search_call(cfg->num_simulations, cfg->max_depth, n, root_logits, root_value, root_embedding,
+                                   legal_bits, workspace, workspace_bytes, search_workspace_bytes, action,
+                                   action_weights, root_value_out);
+  if (rc || n == 0) return rc;
   return launch_gumbel_search(*w, make_search_args(*cfg), root_logits, root_value, root_embedding, legal_bits, gumbel, game_id, n, nullptr,
                               workspace, action, action_weights, root_value_out, (hipStream_t)stream);
 }

@@ -549,11 +549,11 @@ int muz_stochastic_search(const muz_classic_net_w* w, const muz_stoch_cfg* cfg, 
                           float* root_value_out, void* stream) {
   int rc = check_classic_net(w);
   if (rc) return rc;
-  MUZ_HOST_CHECK(cfg && root_logits && root_value && root_embedding && legal_bits && workspace && action &&
-                 action_weights && root_value_out && n >= 0);
-  if (check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
-  MUZ_HOST_CHECK(workspace_bytes >= stochastic_workspace_bytes(n, cfg->num_simulations));
-  if (n == 0) return MUZ_OK;
+  MUZ_HOST_CHECK(cfg);
+  rc = check_search_call(cfg->num_simulations, cfg->max_depth, n, root_logits, root_value, root_embedding, legal_bits,
+                         workspace, workspace_bytes, stochastic_workspace_bytes, action, action_weights,
+                         root_value_out);
+  if (rc || n == 0) return rc;
   return launch_stochastic_search(*w, make_sargs(*cfg, w->num_actions), root_logits, root_value, root_embedding,
                                   legal_bits, dirichlet, gumbel, game_id, n, nullptr, workspace, action, action_weights,
                                   root_value_out, (hipStream_t)stream);

@@ -1,7 +1,12 @@
-// The tree machinery the persistent search kernels share (k_gumbel_search, k_puct_search, k_stochastic_search, k_dog_search): one
-// game per kRowLanes lanes, node scalars and the current path in LDS, children arrays and node embeddings in the
-// workspace.  The limits (kMaxSims, kMaxNodes, kMaxDepth) sit beside SearchArgs in launch.hpp, where the host entry
-// points read them too.
+// The tree machinery the persistent search kernels share: one game per kRowLanes lanes, node scalars and the current
+// path in LDS, children arrays and node embeddings in the workspace.  k_gumbel_search and k_puct_search are built from
+// one simulation body -- SearchLds (the per-row LDS state), NarrowTree::kid (a node's children), walk (the selection
+// loop around the kernel's score), commit_expansion and commit_backup -- and differ in their root, score and tail.
+// k_stochastic_search shares the tree layout and row_argmax and keeps its own walk, expansion and one-lane backup
+// written out (on the shared body it was 0.3 % slower per classic self-play step, and needed 247 VGPRs with
+// commit_backup: profiles/search_body_refactor.log); k_dog_search (806 children per node, its own walk and backup)
+// shares row_argmax and exp_cr.  The limits (kMaxSims, kMaxNodes, kMaxDepth) sit beside SearchArgs in launch.hpp, where
+// the host entry points read them too.
 #pragma once
 #include "launch.hpp"
 #include "nn.hpp"
@@ -10,6 +15,18 @@ namespace muz {
 inline namespace MUZ_NN_NS {   // (built on tid(): see the note at the top of nn.hpp)
 
 constexpr float kFMin = -3.4028234663852886e38f;   // jnp.finfo(float32).min
+
+// Dyn4's reward / discount trunk inside Pred4's Dense_1 phase (nn.hpp pred16 LATE_HEADS)
+#ifndef MUZ_LATE_HEADS
+#define MUZ_LATE_HEADS 0
+#endif
+constexpr bool kLateHeads = MUZ_LATE_HEADS != 0;
+// levels per backup chunk (one per lane; backup_lanes).  A smaller value (make EXTRA=-DMUZ_BACKUP_CHUNK=4) runs the
+// chunked path of max_depth > 32 at ordinary depths; no committed test builds that variant
+#ifndef MUZ_BACKUP_CHUNK
+#define MUZ_BACKUP_CHUNK kRowLanes
+#endif
+constexpr int kBackupChunk = MUZ_BACKUP_CHUNK;
 
 // (value, index) argmax across the row's lanes under the order "larger value, then smaller index" (jnp.argmax
 // tie-break: the first index)
@@ -61,7 +78,7 @@ __device__ __forceinline__ float row_sum24(float v) {
   return v + dpp<DPP_HALF_MIRROR>(v);           // lane i <-> 7 - i: the two halves
 }
 
-// One child edge of the current node, held by lane `a` of the game's 32 lanes (ok = a < A).
+// One child edge of the current node, held by lane `a` of the game's 32 lanes (ok: a real child slot, a < A).
 struct Kid {
   float prior, value, reward, disc;
   int visits, index;
@@ -112,6 +129,19 @@ struct NarrowTree : Arrays {
   __device__ __forceinline__ AS1 int32_t* visits() const { return gpw(this->c_visits); }
   __device__ __forceinline__ AS1 float* reward() const { return gpw(this->c_reward); }
   __device__ __forceinline__ AS1 float* disc() const { return gpw(this->c_disc); }
+  // child a of `node` (lanes past the real slots, !ok: slot 0's words with no visits)
+  __device__ __forceinline__ Kid kid(int g, int node, int a, bool ok) const {
+    Kid k;
+    const size_t e = ca(g, node, ok ? a : 0);
+    k.ok = ok;
+    k.prior = tree_ld(prior() + e);
+    k.value = tree_ld(value() + e);
+    k.reward = tree_ld(reward() + e);
+    k.disc = tree_ld(disc() + e);
+    k.visits = ok ? tree_ld(visits() + e) : 0;
+    k.index = tree_ld(index() + e);
+    return k;
+  }
 
   static size_t child_bytes(int64_t n, int N) { return (size_t)n * N * APAD * 4; }
   static size_t bytes(int64_t n, int N) { return 6 * child_bytes(n, N) + (size_t)n * N * LAT * 4; }
@@ -130,6 +160,8 @@ struct NarrowTree : Arrays {
     return t;
   }
 };
+// the det-MADN searches' tree (k_gumbel_search, k_puct_search): children arrays padded to 32 actions
+using TreeWs = NarrowTree<32>;
 
 // One row's recorded path (an entry per level: node, chosen child, the child's visit-count word, its reward and
 // discount) and its node statistics, all in LDS.
@@ -190,6 +222,130 @@ __device__ __forceinline__ void backup_lanes(const PathRow& p, int a, int d, flo
     }
     carry = __shfl(leaf, 0, kRowLanes);
     carry_v = __shfl(pv, 0, kRowLanes);
+  }
+}
+
+// Where a walk ended: the node to expand from, the action taken there, the child already at that edge (-1: none yet)
+// and the path's depth.
+struct WalkEnd {
+  int node, act, next, depth;
+};
+
+// The per-row LDS state of a search over a narrow tree (one __shared__ object per kernel): node statistics, the
+// recorded path and the walk's hand-off to the expand phase.
+struct SearchLds {
+  int visits[kRows][kMaxNodes];
+  float val[kRows][kMaxNodes];
+  int p_node[kRows][kMaxDepth];
+  int p_act[kRows][kMaxDepth];
+  int p_cvis[kRows][kMaxDepth];
+  float p_rew[kRows][kMaxDepth];
+  float p_disc[kRows][kMaxDepth];
+  int act[kRows], parent[kRows], next[kRows], depth[kRows];
+  float rootv[kRows];
+
+  __device__ __forceinline__ PathRow path(int row) {
+    return PathRow{p_node[row], p_act[row], p_cvis[row], p_rew[row], p_disc[row], visits[row], val[row]};
+  }
+  // (one lane of the row) the walk's end for the expand phase; a path that ends at a missing child creates node
+  // sim + 1
+  __device__ __forceinline__ void hand_off(int row, const WalkEnd& w, int sim) {
+    parent[row] = w.node;
+    act[row] = w.act;
+    next[row] = (w.next == -1) ? sim + 1 : w.next;
+    depth[row] = w.depth;
+  }
+};
+
+// search.py simulate for this lane's game: from the root (its children: rk, in registers) take the child with the
+// largest score(kid, node, depth) -- this lane's score, -INFINITY for a lane that may not be chosen -- at every level,
+// recording the path, until the chosen edge has no child yet or max_depth levels are taken.
+template <class Tree, class Score>
+__device__ __forceinline__ WalkEnd walk(const Tree& T, SearchLds& L, const Kid& rk, int max_depth, Score score) {
+  const int row = trow(), a = tsub();
+  const int g = blockIdx.x * kRows + row;
+  int node = 0, depth = 0;
+  while (true) {
+    const Kid k = depth == 0 ? rk : T.kid(g, node, a, rk.ok);
+    float sc = score(k, node, depth);
+    int bi = a;
+    row_argmax(sc, bi);
+    const int child = __shfl(k.index, bi, kRowLanes);
+    if (a == bi) {
+      L.p_node[row][depth] = node;
+      L.p_act[row][depth] = bi;
+      L.p_rew[row][depth] = k.reward;
+      L.p_disc[row][depth] = k.disc;
+      L.p_cvis[row][depth] = k.visits;
+    }
+    ++depth;
+    if (child == -1 || depth >= max_depth) return WalkEnd{node, bi, child, depth};
+    node = child;
+  }
+}
+
+// search.py expand's bookkeeping for node L.next[row] (fresh when it is node sim + 1): this lane's child slot gets
+// `prior` (a fresh node's other five words are initialised), the edge L.parent[row] -- L.act[row] is linked to the
+// node with its reward and discount (a root edge: rk, registers; else the tree) and the node takes value v and one
+// more visit.
+template <class Tree>
+__device__ __forceinline__ void commit_expansion(const Tree& T, SearchLds& L, Kid& rk, int sim, float prior, float v,
+                                                 float rw, float dc) {
+  const int row = trow(), a = tsub();
+  const int g = blockIdx.x * kRows + row;
+  const int nx = L.next[row];
+  const bool fresh = nx == sim + 1;
+  if (rk.ok) {
+    const size_t nb = T.ca(g, nx, a);
+    tree_st(T.prior() + nb, prior);
+    if (fresh) {
+      tree_st(T.index() + nb, -1);
+      tree_st(T.visits() + nb, 0);
+      tree_st(T.value() + nb, 0.f);
+      tree_st(T.reward() + nb, 0.f);
+      tree_st(T.disc() + nb, 0.f);
+    }
+  }
+  const int par = L.parent[row], pa = L.act[row];
+  if (par == 0 && a == pa) {   // a root edge: registers
+    rk.index = nx;
+    rk.reward = rw;
+    rk.disc = dc;
+  }
+  if (a == 0) {
+    if (par != 0) {
+      const size_t eb = T.ca(g, par, pa);
+      tree_st(T.index() + eb, nx);
+      tree_st(T.reward() + eb, rw);
+      tree_st(T.disc() + eb, dc);
+    }
+    L.val[row][nx] = v;
+    L.visits[row][nx] = fresh ? 1 : L.visits[row][nx] + 1;
+  }
+}
+
+// search.py backward along the recorded path (backup_lanes): an interior edge's new value and visit count go to the
+// tree, the root edge's (level 0: registers) through L.rootv to the lane that holds it.
+template <class Tree>
+__device__ __forceinline__ void commit_backup(const Tree& T, SearchLds& L, Kid& rk, float v, float rw, float dc) {
+  const int row = trow(), a = tsub();
+  const int g = blockIdx.x * kRows + row;
+  backup_lanes<kBackupChunk>(L.path(row), a, L.depth[row], v, rw, dc,
+                             [&](int l, int parent, int pact, int cvis, float, float, float child_v) {
+                               if (l > 0) {
+                                 const size_t ei = T.ca(g, parent, pact);
+                                 tree_st(T.value() + ei, child_v);
+                                 tree_st(T.visits() + ei, cvis + 1);
+                               } else {
+                                 L.rootv[row] = child_v;
+                               }
+                             });
+  // the root edge of this path (level 0): its lane takes the value lane 0 just backed up
+  // (same wave: LDS operations of one wave complete in order)
+  __builtin_amdgcn_wave_barrier();
+  if (a == L.p_act[row][0]) {
+    rk.value = L.rootv[row];
+    rk.visits += 1;
   }
 }
 
