@@ -82,6 +82,9 @@ struct PuctArgs {
   float min_value, max_value, dir_frac, dir_alpha, pb_c_init, pb_c_base, temperature;
   unsigned long long seed;
   int turn;
+  // optional noise keys of a self-play driver (see SearchArgs): game id key_game[lane], turn key_turn[game id]
+  const int32_t* key_game = nullptr;
+  const int32_t* key_turn = nullptr;
 };
 static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
   PuctArgs pa;
@@ -99,10 +102,18 @@ static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
   pa.turn = cfg.turn;
   return pa;
 }
+// muz_puct_cfg's own settings, as every entry point that takes one refuses them (written so that a NaN is refused too)
+static inline int check_puct_cfg(const muz_puct_cfg& cfg) {
+  if (cfg.qtransform != MUZ_QT_MIN_MAX && cfg.qtransform != MUZ_QT_PARENT_SIBLINGS) return MUZ_E_UNSUPPORTED;
+  if (!(cfg.max_value > cfg.min_value)) return MUZ_E_UNSUPPORTED;
+  if (!(cfg.dirichlet_fraction >= 0.f && cfg.dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
+  if (!(cfg.dirichlet_alpha > 0.f) || !(cfg.pb_c_base > 0.f) || !(cfg.temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
+  return MUZ_OK;
+}
 int launch_puct_search(const muz_net_w& w, const PuctArgs& pa, const float* root_logits, const float* root_value,
                        const float* root_emb, const uint32_t* legal, const float* dirichlet, const float* gumbel,
-                       const int32_t* game_id, int n, void* workspace, int32_t* action, float* weights, float* value,
-                       hipStream_t s);
+                       const int32_t* game_id, int n, const int* n_dev, void* workspace, int32_t* action,
+                       float* weights, float* value, hipStream_t s);
 
 // Stochastic MuZero (stochastic.hip)
 struct SArgs {

@@ -51,14 +51,15 @@ template <int QT>
 __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     muz_net_w Wt, PuctArgs pa, const float* __restrict__ root_logits, const float* __restrict__ root_value,
     const float* __restrict__ root_emb, const uint32_t* __restrict__ legal, const float* __restrict__ dirichlet_in,
-    const float* __restrict__ gumbel_in, const int32_t* __restrict__ game_id, int n, TreeWs T, int32_t* out_action,
-    float* out_weights, float* out_value) {
+    const float* __restrict__ gumbel_in, const int32_t* __restrict__ game_id, int n, const int* __restrict__ n_dev,
+    TreeWs T, int32_t* out_action, float* out_weights, float* out_value) {
   // tree arithmetic exactly as written; the networks (nn.hpp) keep their own contraction
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
   __shared__ SearchLds L;
   __shared__ float s_pbtab[kMaxNodes + 1];   // sqrt(N) * pb_c(N) for a node's visit count N = 0..S+1
 
+  if (n_dev) n = *n_dev;
   if ((int)blockIdx.x * kRows >= n) return;
   const Arena ar = Arena::carve(smem);
   const int A = Wt.num_actions;
@@ -89,7 +90,10 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
   bool inv = true;
   if (valid) {
     lb = legal[g];
-    gid = game_id ? game_id[g] : g;
+    // the noise keys of every draw below (see SearchArgs): the game's number and its own step count
+    const int lane = game_id ? game_id[g] : g;
+    gid = pa.key_game ? pa.key_game[lane] : lane;
+    gturn = pa.key_turn ? pa.key_turn[gid] : pa.turn;
     inv = !ok || ((lb >> a) & 1u) == 0u;
     const float pr = row_softmax24(ok ? root_logits[(size_t)g * A + ai] : 0.f, ok);
     float dn = 0.f;
@@ -183,17 +187,17 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
 
 int launch_puct_search(const muz_net_w& w, const PuctArgs& pa, const float* root_logits, const float* root_value,
                        const float* root_emb, const uint32_t* legal, const float* dirichlet, const float* gumbel,
-                       const int32_t* game_id, int n, void* workspace, int32_t* action, float* weights, float* value,
-                       hipStream_t s) {
+                       const int32_t* game_id, int n, const int* n_dev, void* workspace, int32_t* action,
+                       float* weights, float* value, hipStream_t s) {
   const TreeWs T = TreeWs::carve(workspace, n, pa.S + 1);
   const dim3 grid((n + kRows - 1) / kRows);
   if (pa.qtransform == MUZ_QT_MIN_MAX)
     k_puct_search<MUZ_QT_MIN_MAX><<<grid, kThreads, 0, s>>>(w, pa, root_logits, root_value, root_emb, legal, dirichlet,
-                                                            gumbel, game_id, n, T, action, weights, value);
+                                                            gumbel, game_id, n, n_dev, T, action, weights, value);
   else
     k_puct_search<MUZ_QT_PARENT_SIBLINGS><<<grid, kThreads, 0, s>>>(w, pa, root_logits, root_value, root_emb, legal,
-                                                                    dirichlet, gumbel, game_id, n, T, action, weights,
-                                                                    value);
+                                                                    dirichlet, gumbel, game_id, n, n_dev, T, action,
+                                                                    weights, value);
   return muz_last_launch_error();
 }
 
@@ -209,17 +213,14 @@ int muz_puct_search(const muz_net_w* w, const muz_puct_cfg* cfg, const float* ro
                     int32_t* action, float* action_weights, float* root_value_out, void* stream) {
   if (!w || !cfg) return MUZ_E_INVALID;
   if (w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
-  if (cfg->qtransform != MUZ_QT_MIN_MAX && cfg->qtransform != MUZ_QT_PARENT_SIBLINGS) return MUZ_E_UNSUPPORTED;
-  // (written so that a NaN is refused too)
-  if (!(cfg->max_value > cfg->min_value)) return MUZ_E_UNSUPPORTED;
-  if (!(cfg->dirichlet_fraction >= 0.f && cfg->dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
-  if (!(cfg->dirichlet_alpha > 0.f) || !(cfg->pb_c_base > 0.f) || !(cfg->temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
+  if (check_puct_cfg(*cfg)) return MUZ_E_UNSUPPORTED;
   const int rc = check_search_call(cfg->num_simulations, cfg->max_depth, n, root_logits, root_value, root_embedding,
                                    legal_bits, workspace, workspace_bytes, search_workspace_bytes, action,
                                    action_weights, root_value_out);
   if (rc || n == 0) return rc;
   return launch_puct_search(*w, make_puct_args(*cfg), root_logits, root_value, root_embedding, legal_bits, dirichlet,
-                            gumbel, game_id, n, workspace, action, action_weights, root_value_out, (hipStream_t)stream);
+                            gumbel, game_id, n, nullptr, workspace, action, action_weights, root_value_out,
+                            (hipStream_t)stream);
 }
 
 }  // extern "C"

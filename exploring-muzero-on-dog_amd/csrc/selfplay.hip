@@ -3,9 +3,9 @@
 //
 // Per turn: legal masks + active flags for every game -> deterministic device compaction of the
 // games that search (has a legal move) -> encode their observations -> root inference ->
-// persistent Gumbel search -> env_step / no_step + trajectory records.  Unlike the reference's
-// vmap-of-cond, finished games and no-move turns cost no network work, and there is no host round
-// trip inside a turn: batch sizes live on the device (`counts`), surplus workgroups exit early.
+// persistent search (Gumbel, or muzero_policy's PUCT: muz_detmadn_selfplay_puct) -> env_step / no_step +
+// trajectory records.  Unlike the reference's vmap-of-cond, finished games and no-move turns cost no
+// network work, and there is no host round trip inside a turn: batch sizes live on the device (`counts`), surplus workgroups exit early.
 // The host checks the active-game count two turns late (pinned memory + events), so the GPU queue
 // never drains; the at most two trailing turns it launches find no active game and record nothing.
 // The streaming driver's turn head also plays no-move turns where it finds them (fast-forward, k_sp_head), so a
@@ -397,17 +397,47 @@ static int sp_fastforward_cap() {
   return kSpFfCap;
 }
 
+// The turn's search, as sp_turns launches it: the compacted batch (ws.legal_c, ws.list as game_id, `counts` as the
+// device-resident row count) into the per-slot ws.action / ws.weights / ws.value, noise keyed by the game's number
+// (key_game = lane_game) and its own step count (key_turn = tr.idx, == the turn for every game of a batch).
+struct GumbelTurn {
+  SearchArgs sa;
+  GumbelTurn(const muz_search_cfg& cfg, const int32_t* lane_game, const int32_t* idx) : sa(make_search_args(cfg)) {
+    sa.key_turn = idx;
+    sa.key_game = lane_game;
+  }
+  int operator()(const muz_net_w& w, const SpWs& ws, int n, const int* counts, int turn, hipStream_t s) {
+    sa.turn = turn;
+    return launch_gumbel_search(w, sa, ws.root_logits, ws.root_value, ws.root_emb, ws.legal_c, nullptr, ws.list, n,
+                                counts, ws.tree, ws.action, ws.weights, ws.value, s);
+  }
+};
+// muzero_policy (puct_search.hip) on the same tree workspace; Dirichlet, tie-break and final-draw noise from the
+// counter RNG (cfg.turn is not used: key_turn is set for both drivers)
+struct PuctTurn {
+  PuctArgs pa;
+  PuctTurn(const muz_puct_cfg& cfg, const int32_t* lane_game, const int32_t* idx) : pa(make_puct_args(cfg)) {
+    pa.key_turn = idx;
+    pa.key_game = lane_game;
+  }
+  int operator()(const muz_net_w& w, const SpWs& ws, int n, const int* counts, int turn, hipStream_t s) {
+    pa.turn = turn;
+    return launch_puct_search(w, pa, ws.root_logits, ws.root_value, ws.root_emb, ws.legal_c, nullptr, nullptr, ws.list,
+                              n, counts, ws.tree, ws.action, ws.weights, ws.value, s);
+  }
+};
+static int check_policy_cfg(const muz_search_cfg&) { return MUZ_OK; }
+static int check_policy_cfg(const muz_puct_cfg& cfg) { return check_puct_cfg(cfg); }
+
 // The turn loop shared by the batch and the streaming driver.  Batch: lane g plays game g for at most T
 // turns.  Streaming (lane_game != null): lanes are refilled with the next game number when theirs ends,
-// until num_games games have been played.
-static int sp_turns(const DetConsts& c, const muz_net_w* w, const muz_search_cfg* cfg, muz_detmadn_soa st, muz_traj tr,
+// until num_games games have been played.  Search: GumbelTurn or PuctTurn.
+template <class Search>
+static int sp_turns(const DetConsts& c, const muz_net_w* w, Search search, muz_detmadn_soa st, muz_traj tr,
                     int n, const SpWs& ws, const int32_t* lane_game, int num_games, int max_turns, int ff_cap,
                     muz_sp_stats* stats, hipStream_t s) {
   const int T = tr.max_steps;
   int rc = MUZ_OK;
-  SearchArgs sa = make_search_args(*cfg);   // (sa.turn: set per turn below)
-  sa.key_turn = tr.idx;  // the game's own step count (== the turn for every game of a batch)
-  sa.key_game = lane_game;
 
   TurnLedger led(s, stats != nullptr);
   if ((rc = led.begin())) return rc;
@@ -441,11 +471,8 @@ static int sp_turns(const DetConsts& c, const muz_net_w* w, const muz_search_cfg
                                     s, host_counts)))
       break;
     if (host_counts) led.counts_written(turn);
-    sa.turn = turn;
     led.search_begin(turn);
-    if ((rc = launch_gumbel_search(*w, sa, ws.root_logits, ws.root_value, ws.root_emb, ws.legal_c, nullptr, ws.list, n, counts, ws.tree, ws.action, ws.weights,
-                                   ws.value, s)))
-      break;
+    if ((rc = search(*w, ws, n, counts, turn, s))) break;
     led.search_end(turn);
     pending = true;   // applied by the next turn's head (or after the loop)
     if ((rc = muz_last_launch_error())) break;
@@ -464,20 +491,53 @@ static size_t det_carve(char* base, int n, int C, int S, SpWs* ws) {
   return sp_carve(base, n, C, MUZ_DET_ACTIONS, (size_t)search_workspace_bytes(n, S), ws);
 }
 
-// The checks of both entry points (`lanes` games at a time out of num_games), then the carve
-static int sp_setup(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg, const muz_detmadn_soa& st,
+// The checks of every entry point (`lanes` games at a time out of num_games; Cfg: muz_search_cfg or muz_puct_cfg, the
+// policy's own settings refused as its search entry point refuses them), then the carve
+template <class Cfg>
+static int sp_setup(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, const muz_detmadn_soa& st,
                     const muz_traj& tr, int lanes, int num_games, void* workspace, int64_t workspace_bytes,
                     muz_sp_stats* stats, DetConsts* c, SpWs* ws) {
   int rc = make_det_consts(rules, c);
   if (rc) return rc;
   if (!w || !cfg) return MUZ_E_INVALID;
   if (w->obs_channels != 8 * c->P + 2 || w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
+  if ((rc = check_policy_cfg(*cfg))) return rc;
   MUZ_HOST_CHECK(sp_args_ok(lanes, num_games, st.stride, workspace, tr, true));
   if ((rc = check_search_limits(cfg->num_simulations, cfg->max_depth))) return rc;
   if (stats) *stats = muz_sp_stats{};
   MUZ_HOST_CHECK(workspace_bytes >= (int64_t)det_carve(nullptr, lanes, w->obs_channels, cfg->num_simulations, nullptr));
   det_carve((char*)workspace, lanes, w->obs_channels, cfg->num_simulations, ws);
   return MUZ_OK;
+}
+
+// play_n_games_v3 with either search: batch_reset + zeroed buffers, then the turn loop
+template <class Search, class Cfg>
+static int sp_batch(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, muz_detmadn_soa st, muz_traj tr, int n,
+                    void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, hipStream_t s) {
+  DetConsts c;
+  SpWs ws;
+  int rc = sp_setup(rules, w, cfg, st, tr, n, n, workspace, workspace_bytes, stats, &c, &ws);
+  if (rc || n == 0) return rc;
+  k_det_reset_sp<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
+  if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
+  return sp_turns(c, w, Search(*cfg, nullptr, tr.idx), st, tr, n, ws, nullptr, n, tr.max_steps, 0, stats, s);
+}
+
+template <class Search, class Cfg>
+static int sp_stream(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, muz_detmadn_soa st, muz_traj tr,
+                     int num_games, int lanes, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
+                     hipStream_t s) {
+  DetConsts c;
+  SpWs ws;
+  const int n = lanes;
+  int rc = sp_setup(rules, w, cfg, st, tr, n, num_games, workspace, workspace_bytes, stats, &c, &ws);
+  if (rc || n == 0 || num_games == 0) return rc;
+  if ((rc = traj_clear(tr, num_games, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
+  // lane l starts game l (l < num_games); later games are handed out by the turn head's refill
+  k_ss_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
+  MUZ_HIP_RET(hipGetLastError());
+  return sp_turns(c, w, Search(*cfg, ws.lane_game, tr.idx), st, tr, n, ws, ws.lane_game, num_games,
+                  stream_max_turns(num_games, n, tr.max_steps), sp_fastforward_cap(), stats, s);
 }
 
 }  // namespace muz
@@ -494,32 +554,27 @@ int64_t muz_selfplay_workspace_bytes(int32_t n, int32_t obs_channels, const muz_
 int muz_detmadn_selfplay(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg, muz_detmadn_soa st,
                          muz_traj tr, int32_t n, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
                          void* stream) {
-  DetConsts c;
-  SpWs ws;
-  int rc = sp_setup(rules, w, cfg, st, tr, n, n, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  // play_n_games_v3: batch_reset + zeroed buffers
-  k_det_reset_sp<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
-  if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
-  return sp_turns(c, w, cfg, st, tr, n, ws, nullptr, n, tr.max_steps, 0, stats, s);
+  return sp_batch<GumbelTurn>(rules, w, cfg, st, tr, n, workspace, workspace_bytes, stats, (hipStream_t)stream);
 }
 
 int muz_detmadn_selfplay_stream(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg,
                                 muz_detmadn_soa st, muz_traj tr, int32_t num_games, int32_t lanes, void* workspace,
                                 int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
-  DetConsts c;
-  SpWs ws;
-  const int n = lanes;
-  int rc = sp_setup(rules, w, cfg, st, tr, n, num_games, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0 || num_games == 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = traj_clear(tr, num_games, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
-  // lane l starts game l (l < num_games); later games are handed out by the turn head's refill
-  k_ss_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
-  MUZ_HIP_RET(hipGetLastError());
-  return sp_turns(c, w, cfg, st, tr, n, ws, ws.lane_game, num_games, stream_max_turns(num_games, n, tr.max_steps),
-                  sp_fastforward_cap(), stats, s);
+  return sp_stream<GumbelTurn>(rules, w, cfg, st, tr, num_games, lanes, workspace, workspace_bytes, stats,
+                               (hipStream_t)stream);
+}
+
+int muz_detmadn_selfplay_puct(const muz_rules* rules, const muz_net_w* w, const muz_puct_cfg* cfg, muz_detmadn_soa st,
+                              muz_traj tr, int32_t n, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
+                              void* stream) {
+  return sp_batch<PuctTurn>(rules, w, cfg, st, tr, n, workspace, workspace_bytes, stats, (hipStream_t)stream);
+}
+
+int muz_detmadn_selfplay_puct_stream(const muz_rules* rules, const muz_net_w* w, const muz_puct_cfg* cfg,
+                                     muz_detmadn_soa st, muz_traj tr, int32_t num_games, int32_t lanes,
+                                     void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
+  return sp_stream<PuctTurn>(rules, w, cfg, st, tr, num_games, lanes, workspace, workspace_bytes, stats,
+                             (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -2,7 +2,7 @@
 
 ``play_n_games_v3`` keeps the reference signature's meaning (game_agent.py:185-192): reset
 ``num_envs`` games, play them to completion (or ``max_steps`` batched turns) with a Gumbel-MuZero
-search per move, and return the trajectory buffers as a dict of device tensors
+search per move (``policy="puct"``: the reference's commented mctx.muzero_policy call instead), and return the trajectory buffers as a dict of device tensors
 (obs, act, rew, val, pol, mask, player, team, discount, idx) shaped [num_envs, max_steps, ...].
 The whole loop runs natively in libmuz.so (muz_detmadn_selfplay): no per-turn Python, no
 host<->device copy inside a turn.  ``obs`` is int8 (values 0..4); the reference stores fp32.
@@ -20,6 +20,21 @@ from . import nets as N
 
 # MuZero_det_MADN/game_agent.py:12-22
 RULES = dict(E.SELFPLAY_RULES)
+POLICIES = ("gumbel", "puct")
+PUCT_KWARGS = ("qtransform", "min_value", "max_value", "dirichlet_fraction", "dirichlet_alpha", "pb_c_init", "pb_c_base")
+
+
+def check_policy(policy, policy_kwargs) -> dict:
+    """The rule of mcts.muzero_mcts: an unknown policy is a ValueError, PUCT keywords on the Gumbel path (or unknown
+    ones on the PUCT path) a TypeError.  -> the keywords as a dict."""
+    kw = dict(policy_kwargs or {})
+    if policy not in POLICIES:
+        raise ValueError(f"unknown policy {policy!r} ('gumbel' or 'puct')")
+    if policy == "gumbel" and kw:
+        raise TypeError(f"policy='gumbel' takes no {sorted(kw)}")
+    if set(kw) - set(PUCT_KWARGS):
+        raise TypeError(f"policy='puct' takes no {sorted(set(kw) - set(PUCT_KWARGS))}")
+    return kw
 
 
 class SelfPlayEngine:
@@ -27,7 +42,11 @@ class SelfPlayEngine:
 
     def __init__(self, net: N.DeviceNet, num_envs: int, num_players: int = 4, max_steps: int = 550,
                  num_simulations: int = 50, max_depth: int = 25, rules: dict | None = None, starting_player=0,
-                 device="cuda"):
+                 device="cuda", policy: str = "gumbel", policy_kwargs: dict | None = None):
+        """``policy="puct"`` plays with mctx.muzero_policy (mcts.muzero_policy; ``policy_kwargs``: qtransform,
+        min_value, max_value, dirichlet_fraction, dirichlet_alpha, pb_c_init, pb_c_base); the records' ``pol`` are then
+        the root visit fractions.  The workspace is the same for both policies."""
+        self.policy, self.policy_kwargs = policy, check_policy(policy, policy_kwargs)   # (before any allocation)
         self.net = net
         self.n, self.P, self.T = int(num_envs), int(num_players), int(max_steps)
         self.S, self.D = int(num_simulations), int(max_depth)
@@ -65,16 +84,23 @@ class SelfPlayEngine:
         t.max_steps = self.T
         return t
 
+    def _search(self, seed, temperature):
+        """-> (the call's search configuration, the batch entry point's name, the streaming one's)."""
+        if self.policy == "puct":
+            return (M.make_puct_cfg(self.S, self.D, temperature, seed=seed, **self.policy_kwargs),
+                    "muz_detmadn_selfplay_puct", "muz_detmadn_selfplay_puct_stream")
+        return (M.make_cfg(self.S, self.D, temperature=temperature, seed=seed), "muz_detmadn_selfplay",
+                "muz_detmadn_selfplay_stream")
+
     def play(self, seed: int, temperature: float = 1.0, stream=None, timing: bool = True) -> dict:
         """One play_n_games_v3 call.  The native loop synchronises its stream before returning.
         With ``timing`` the search launches are bracketed by HIP events (see ``last_stats``)."""
         lib = _L.load()
-        cfg = M.make_cfg(self.S, self.D, temperature=temperature, seed=seed)
+        cfg, name, _ = self._search(seed, temperature)
         st = _L.MuzSpStats()
-        _L.check(lib.muz_detmadn_selfplay(self.rules, self.net.w, cfg, self.state.soa(), self.traj(), self.n,
-                                          _L.ptr(self.workspace), _L.nbytes(self.workspace),
-                                          ctypes.byref(st) if timing else None,
-                                          _L.stream_ptr(stream)), "muz_detmadn_selfplay")
+        _L.check(getattr(lib, name)(self.rules, self.net.w, cfg, self.state.soa(), self.traj(), self.n,
+                                    _L.ptr(self.workspace), _L.nbytes(self.workspace),
+                                    ctypes.byref(st) if timing else None, _L.stream_ptr(stream)), name)
         self.last_stats = {"turns": st.turns, "searches": st.searches, "search_ms": st.search_ms,
                            "total_ms": st.total_ms} if timing else None
         self.last_turns = st.turns if timing else -1
@@ -98,12 +124,11 @@ class SelfPlayEngine:
         for k in ("obs", "act", "rew", "val", "pol", "mask", "player", "team", "discount", "idx"):
             setattr(t, k, self._sbuf[k].data_ptr())
         t.max_steps = self.T
-        cfg = M.make_cfg(self.S, self.D, temperature=temperature, seed=seed)
+        cfg, _, name = self._search(seed, temperature)
         st = _L.MuzSpStats()
-        _L.check(lib.muz_detmadn_selfplay_stream(self.rules, self.net.w, cfg, self.state.soa(), t, num_games, self.n,
-                                                 _L.ptr(self.workspace), _L.nbytes(self.workspace),
-                                                 ctypes.byref(st) if timing else None, _L.stream_ptr(stream)),
-                 "muz_detmadn_selfplay_stream")
+        _L.check(getattr(lib, name)(self.rules, self.net.w, cfg, self.state.soa(), t, num_games, self.n,
+                                    _L.ptr(self.workspace), _L.nbytes(self.workspace),
+                                    ctypes.byref(st) if timing else None, _L.stream_ptr(stream)), name)
         self.last_stats = {"turns": st.turns, "searches": st.searches, "search_ms": st.search_ms,
                            "total_ms": st.total_ms} if timing else None
         self.last_turns = st.turns if timing else -1
@@ -113,18 +138,21 @@ class SelfPlayEngine:
 _ENGINE_CACHE = {}
 
 
-def cached_engine(net: N.DeviceNet, num_envs, num_players, max_steps, num_simulation, max_depth, rules) -> SelfPlayEngine:
-    """The engine of the last reference-signature call, reused when the call's shape, rules and weight set are
-    the same: a test_training-style loop calls play_n_games_v3 once per iteration, and a fresh engine would
+def cached_engine(net: N.DeviceNet, num_envs, num_players, max_steps, num_simulation, max_depth, rules,
+                  policy="gumbel", policy_kwargs=None) -> SelfPlayEngine:
+    """The engine of the last reference-signature call, reused when the call's shape, rules, search policy (and its
+    keywords) and weight set are the same: a test_training-style loop calls play_n_games_v3 once per iteration, and a fresh engine would
     reallocate its state, workspace and [num_envs, max_steps] buffers (GBs at config (e)) every time.  One live
     engine per process (the reference's loops play one configuration at a time)."""
+    kw = check_policy(policy, policy_kwargs)
     key = (id(net), int(num_envs), int(num_players), int(max_steps), int(num_simulation), int(max_depth),
-           tuple(sorted((dict(RULES if rules is None else rules)).items())))
+           tuple(sorted((dict(RULES if rules is None else rules)).items())), policy, tuple(sorted(kw.items())))
     hit = _ENGINE_CACHE.get(key)
     if hit is not None and hit.net is net:
         return hit
     _ENGINE_CACHE.clear()
-    eng = _ENGINE_CACHE[key] = SelfPlayEngine(net, num_envs, num_players, max_steps, num_simulation, max_depth, rules)
+    eng = _ENGINE_CACHE[key] = SelfPlayEngine(net, num_envs, num_players, max_steps, num_simulation, max_depth, rules,
+                                              policy=policy, policy_kwargs=kw)
     return eng
 
 
@@ -149,7 +177,7 @@ def reference_buffers(buf: dict, dtypes: dict) -> dict:
 
 
 def play_n_games_v3(params, rng_key, input_shape, num_envs, num_simulation, max_depth, max_steps, temp,
-                    rules: dict | None = None, obs_dtype=torch.float32) -> dict:
+                    rules: dict | None = None, obs_dtype=torch.float32, policy="gumbel", policy_kwargs=None) -> dict:
     """play_n_games_v3 (MuZero_det_MADN/game_agent.py:185-192), reference signature.
 
     ``params``: init_muzero_params' nested Flax dict (or a flat dict / DeviceNet, nets.as_device_net);
@@ -158,11 +186,16 @@ def play_n_games_v3(params, rng_key, input_shape, num_envs, num_simulation, max_
     plays P = 4, C = 34).  Returns the reference's buffer dict (game_agent.py:158-169): obs fp32
     [num_envs, max_steps, C, 56] (``obs_dtype=torch.int8`` keeps the engine's exact int8 copy), act / rew /
     player / team / discount int32, val / mask fp32, pol fp32 [.., 24], idx int32 -- fresh device tensors, rows past
-    ``idx`` zero (``team`` -1) as the reference initialises them."""
+    ``idx`` zero (``team`` -1) as the reference initialises them.
+
+    ``policy="puct"`` (with ``policy_kwargs``, see SelfPlayEngine) plays what the reference plays once run_muzero_mcts'
+    commented mctx.muzero_policy call (muzero_deterministic_madn.py:685-697) is the live one: ``pol`` holds the root
+    visit fractions."""
+    check_policy(policy, policy_kwargs)
     C = int(input_shape[0])
     if (C - 2) % 8 or int(input_shape[-1]) != E.CELLS:
         raise ValueError(f"input_shape {tuple(input_shape)} is not (8P + 2, 56)")
     net = N.as_device_net(params, C)
-    eng = cached_engine(net, num_envs, (C - 2) // 8, max_steps, num_simulation, max_depth, rules)
+    eng = cached_engine(net, num_envs, (C - 2) // 8, max_steps, num_simulation, max_depth, rules, policy, policy_kwargs)
     buf = eng.play(N.rng_key_to_seed(rng_key), temp)
     return reference_buffers(buf, dict(REFERENCE_DTYPES, obs=obs_dtype))

@@ -448,6 +448,13 @@ SIGNATURES = {
                                                    ctypes.POINTER(MuzSearchCfg), MuzDetSoA, MuzTraj, ctypes.c_int32,
                                                    ctypes.c_int32, vp, ctypes.c_int64, ctypes.POINTER(MuzSpStats),
                                                    vp]),
+    "muz_detmadn_selfplay_puct": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzNetW),
+                                                 ctypes.POINTER(MuzPuctCfg), MuzDetSoA, MuzTraj, ctypes.c_int32, vp,
+                                                 ctypes.c_int64, ctypes.POINTER(MuzSpStats), vp]),
+    "muz_detmadn_selfplay_puct_stream": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzNetW),
+                                                        ctypes.POINTER(MuzPuctCfg), MuzDetSoA, MuzTraj, ctypes.c_int32,
+                                                        ctypes.c_int32, vp, ctypes.c_int64,
+                                                        ctypes.POINTER(MuzSpStats), vp]),
 }
 
 _lib = None

@@ -16,6 +16,7 @@ learner (training.OptState) rather than an optax pytree; checkpoints are written
 """
 from __future__ import annotations
 
+import functools
 import os
 
 from . import detmadn as E
@@ -122,16 +123,28 @@ def _checkpoint_names(cfg, it):
             os.path.join(d, "opt_state", f"Experiment_{cfg['seed']}_{it}.opt_state"))
 
 
+def search_policy(config) -> tuple:
+    """-> (policy, policy_kwargs) of a config: the optional ``search_policy`` ("gumbel", the default, or "puct": the
+    mctx.muzero_policy call run_muzero_mcts keeps commented, :685-697 of muzero_deterministic_madn.py) and
+    ``search_policy_kwargs`` (game_agent.SelfPlayEngine's ``policy_kwargs``)."""
+    policy = config.get("search_policy", "gumbel")
+    return policy, GA.check_policy(policy, config.get("search_policy_kwargs"))
+
+
 def test_training(config, params=None, opt_state=None, log=print):
     """:168-309: 3 warm-up self-play calls into the device ring, then per iteration: the bootstrap switch at
     ``Bootstrap_Switch_Iteration`` (:248-252), self-play of ``num_games_per_iteration`` games with
     get_temperature, the games saved into the ring, ``train_steps_per_iteration`` train steps on sampled
     batches, a checkpoint every ``checkpoint_every`` (100) iterations (:301-307).
+    Self-play searches with ``config["search_policy"]`` (search_policy above; the reference's config has no such key
+    and plays Gumbel).
     -> (params, opt_state, times_per_iteration)."""
+    policy, policy_kwargs = search_policy(config)
+    play = functools.partial(GA.play_n_games_v3, policy=policy, policy_kwargs=policy_kwargs)
     opt = make_optimizer(config) if opt_state is None else None
     input_shape = (E.num_channels(4), E.CELLS)          # :186-205: encode_board of a 4-player reset
     # (self-play uses game_agent's own RULES, as the reference's play_n_games_v3 does)
-    return T.run_training(config, params, opt_state, kind="det", play_n_games_v3=GA.play_n_games_v3,
+    return T.run_training(config, params, opt_state, kind="det", play_n_games_v3=play,
                           make_replay=_replay,
                           optimizer=opt if opt is not None else optimizer, init_params=init_muzero_params,
                           input_shape=input_shape, schedule=TEMPERATURE_SCHEDULE,

@@ -473,7 +473,7 @@ typedef struct muz_sp_stats {
   int32_t turns;      /* batched turns launched that found an active game (a stream that fast-forwards its
                          no-move turns launches fewer of them than its games record turns) */
   int64_t searches;   /* MCTS searches run (sum over turns of games with a legal move) */
-  double search_ms;   /* device time of the Gumbel-search launches */
+  double search_ms;   /* device time of the search launches */
   double total_ms;    /* device time of the whole call */
 } muz_sp_stats;
 
@@ -502,6 +502,31 @@ int muz_detmadn_selfplay_stream(const muz_rules* rules /*host*/, const muz_net_w
                                 const muz_search_cfg* cfg /*host*/, muz_detmadn_soa state, muz_traj traj,
                                 int32_t num_games, int32_t lanes, void* workspace, int64_t workspace_bytes,
                                 muz_sp_stats* stats /*host*/, void* stream);
+
+/* The same self-play with the reference's other policy, the mctx.muzero_policy call run_muzero_mcts keeps commented
+ * (muzero_deterministic_madn.py:685-697; muz_puct_search above): what game_agent.py:50-192 plays once that call is
+ * the live one.  Searches use cfg (S, D, qtransform, Dirichlet root noise, pb_c, temperature of the final draw); the
+ * Dirichlet, tie-break and final-draw noise all come from the counter RNG of cfg->seed, keyed by game number and the
+ * game's own step, so cfg->turn is ignored.  Records: pol = the root visit fractions, val = summary().value (not
+ * clipped).  The workspace is the Gumbel self-play's: at least muz_selfplay_workspace_bytes(n, obs_channels, cfg')
+ * for a muz_search_cfg cfg' with the same num_simulations, 16-byte aligned as traj.obs.
+ * MUZ_E_UNSUPPORTED: what muz_puct_search refuses (num_actions != 24, S or D outside the limits, an unknown
+ * qtransform, max_value <= min_value, dirichlet_fraction outside [0, 1], dirichlet_alpha <= 0, pb_c_base <= 0,
+ * temperature < 0 or NaN) and obs_channels != 8 P + 2.  MUZ_E_INVALID: a null w or cfg, a short or misaligned
+ * workspace, a bad traj.  Checked before any launch; n == 0 returns MUZ_OK. */
+int muz_detmadn_selfplay_puct(const muz_rules* rules /*host*/, const muz_net_w* w /*host*/,
+                              const muz_puct_cfg* cfg /*host*/, muz_detmadn_soa state, muz_traj traj, int32_t n,
+                              void* workspace, int64_t workspace_bytes, muz_sp_stats* stats /*host*/, void* stream);
+
+/* muz_detmadn_selfplay_puct streamed: num_games games through `lanes` refilled lanes (see
+ * muz_detmadn_selfplay_stream, fast-forward and MUZ_SP_FASTFORWARD included).  traj is [num_games][T]; game k's
+ * record, including its Dirichlet, tie-break and final-draw noise (all three keyed by game number and the game's own
+ * step), is identical to game k of a muz_detmadn_selfplay_puct batch of num_games games.  num_games == 0 returns
+ * MUZ_OK. */
+int muz_detmadn_selfplay_puct_stream(const muz_rules* rules /*host*/, const muz_net_w* w /*host*/,
+                                     const muz_puct_cfg* cfg /*host*/, muz_detmadn_soa state, muz_traj traj,
+                                     int32_t num_games, int32_t lanes, void* workspace, int64_t workspace_bytes,
+                                     muz_sp_stats* stats /*host*/, void* stream);
 
 /* ---- Stochastic MuZero for classic MADN (MuZero_Classic_MADN/muzero_classic_madn.py) ----------
  * Same packing conventions as the det networks.  RepresentationNetwork2 (69-135) and
