@@ -45,14 +45,52 @@ __device__ unsigned long long g_muz_stamps[8];
 //    are each ~1 ulp off in different places; the oracle rounds the float64 exp the same way).
 // (row_sum24 and Kid: tree.hpp, shared with k_puct_search)
 
-// qtransform_completed_by_mix_value (value_scale, maxvisit_init, rescale, mixed value, eps 1e-8).
-__device__ __forceinline__ float completed_q(const Kid& k, float raw, const SearchArgs& sa, int& sumv, float& pmax) {
+// The select phase's invariants (kernel template argument PARTS).  What a walk level computes from a node's priors
+// alone -- prior_probs below: one float64 exp, two row reductions, one division -- never changes once the node is
+// expanded, and the root's considered-visit count is a function of (the game's number of considered actions, S, the
+// simulation's index).  Each can be evaluated once instead of at every level:
+//  kSelRoot   the root's prior_probs and largest prior before the simulation loop, kept in registers;
+//  kSelTable  the considered-visit sequence before the loop, a byte table per game in LDS;
+//  kSelNode   a node's prior_probs at its expansion, kept beside its priors (GumbelTree) and loaded with the node's
+//             other words.
+// The expressions are the same functions in every form, so the results are bit for bit the same
+// (tests/test_gpu_select_invariants.py).  MUZ_SELECT_INVARIANTS, read per launch, chooses: unset or 1 -- kSelDefault,
+// the root's two; 0 -- none (the form before these, for A/B runs); 2 -- all three.  kSelNode is off by default: in the
+// stamp build it left the select phase as long as it was and cost 0.8 k cycles per simulation at the expansion
+// (profiles/select_invariants_ab.log).
+// make EXTRA=-DMUZ_SELECT_PARTS=m builds the default form with other parts (a stamp run of one part alone); no
+// committed test builds that variant.
+enum { kSelNode = 1, kSelRoot = 2, kSelTable = 4, kSelAll = 7 };
+#ifndef MUZ_SELECT_PARTS
+#define MUZ_SELECT_PARTS (kSelRoot | kSelTable)
+#endif
+constexpr int kSelDefault = MUZ_SELECT_PARTS;
+
+// The det-MADN tree with prior_probs per child.  Lane a's word lies in the node's pad slots (24..31 of 32) of c_prior
+// (a < 8), c_reward (a < 16) or c_disc: slots nothing else touches, in cache lines the walk loads anyway.
+struct GumbelTree : TreeWs {
+  static_assert(3 * (32 - MUZ_DET_ACTIONS) >= MUZ_DET_ACTIONS, "24 words in the pad slots of three arrays");
+  __device__ __forceinline__ AS1 float* pp(int g, int node, int a) const {
+    AS1 float* const base = a < 8 ? prior() : a < 16 ? reward() : disc();
+    return base + ca(g, node, MUZ_DET_ACTIONS + (a & 7));
+  }
+};
+
+// qtransform_completed_by_mix_value's prior_probs of this lane's child, softmax(prior logits) clamped at the smallest
+// normal float; pm: the row's largest prior logit.
+__device__ __forceinline__ float prior_probs(float prior, bool ok, float& pm) {
+#pragma clang fp contract(off)
+  pm = row_max(ok ? prior : -INFINITY);
+  const float e = ok ? exp_cr(prior - pm) : 0.f;
+  const float es = row_sum24(e);
+  return fmaxf(kTinyF, e / es);
+}
+
+// qtransform_completed_by_mix_value (value_scale, maxvisit_init, rescale, mixed value, eps 1e-8); pp: prior_probs of
+// the node's children.
+__device__ __forceinline__ float completed_q(const Kid& k, float pp, float raw, const SearchArgs& sa, int& sumv) {
 #pragma clang fp contract(off)
   const float q = k.reward + k.disc * k.value;
-  const float pm = row_max(k.ok ? k.prior : -INFINITY);
-  const float e = k.ok ? exp_cr(k.prior - pm) : 0.f;
-  const float es = row_sum24(e);
-  const float pp = fmaxf(kTinyF, e / es);
   const bool vis = k.ok && k.visits > 0;
   const int sv = row_isum(k.ok ? k.visits : 0);
   const int mv = row_imax(k.ok ? k.visits : 0);
@@ -65,20 +103,22 @@ __device__ __forceinline__ float completed_q(const Kid& k, float raw, const Sear
   const float den = fmaxf(hi - lo, 1e-8f);
   const float scale = (sa.maxvisit_init + (float)mv) * sa.value_scale;
   sumv = sv;
-  pmax = pm;
   return scale * ((cq - lo) / den);
 }
 
+template <int PARTS>
 __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     muz_net_w Wt, SearchArgs sa, const float* __restrict__ root_logits, const float* __restrict__ root_value,
     const float* __restrict__ root_emb, const uint32_t* __restrict__ legal, const float* __restrict__ gumbel_in,
-    const int32_t* __restrict__ game_id, int n, const int* __restrict__ n_dev, TreeWs T, int32_t* out_action,
+    const int32_t* __restrict__ game_id, int n, const int* __restrict__ n_dev, GumbelTree T, int32_t* out_action,
     float* out_weights, float* out_value) {
   // tree arithmetic exactly as written (see row_sum24); the networks (nn.hpp) keep their own contraction
 #pragma clang fp contract(off)
   __shared__ __attribute__((aligned(16))) float smem[kArenaFloats];
   __shared__ SearchLds L;
   __shared__ float s_raw[kRows][kMaxNodes];
+  __shared__ uint8_t s_cv[kRows][kMaxSims];   // (CV_TAB) the game's sequence of considered visits
+  constexpr bool NODE_PP = PARTS & kSelNode, ROOT_PP = PARTS & kSelRoot, CV_TAB = PARTS & kSelTable;
 
   if (n_dev) n = *n_dev;
   if ((int)blockIdx.x * kRows >= n) return;
@@ -108,6 +148,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   rk.disc = 0.f;
   rk.visits = 0;
   rk.index = -1;
+  float rpp = 0.f, rpm = 0.f;   // (ROOT_PP) prior_probs of the root's children and its largest prior
   if (valid) {
     lb = legal[g];
     const int lane = game_id ? game_id[g] : g;
@@ -121,6 +162,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     AS1 float* e0 = T.e(g, 0);
     for (int c = a; c < LAT; c += kRowLanes) e0[c] = root_emb[(size_t)g * LAT + c];
     ncons = min(sa.max_considered, __popc(lb & ((1u << A) - 1u)));
+    if constexpr (ROOT_PP) rpp = prior_probs(rk.prior, ok, rpm);
+    // (read by this row's lanes only, one wave)
+    if constexpr (CV_TAB) fill_considered_visits(s_cv[row], ncons, sa.S, a, kRowLanes);
     if (a == 0) {
       const float v = root_value[g];
       L.visits[row][0] = 1;
@@ -130,6 +174,15 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   }
   __syncthreads();
 
+  // CV_TAB: a zero the optimiser cannot see through, for the m of the walk's considered_visit call.  That call's loop
+  // nest is never entered then, but it has to stay in the walk: how the compiler lays out the rest of this kernel
+  // depends on it.  With a plain table read in its place 166 hunks of the networks' MFMA loops come out differently
+  // (pointer arithmetic as add / add-with-carry pairs between the MFMAs) and a launch is 0.5-0.8 % slower than with no
+  // table at all; with the call kept the MFMA loops are instruction for instruction those of the form without the
+  // table and a launch is 1.3-1.9 % faster (B = 4096, S = 50: profiles/select_invariants_ab.log;
+  // profiles/mfma_loop_diff.py counts the hunks).
+  int cv_m0 = 0;
+  if constexpr (CV_TAB) asm volatile("" : "+v"(cv_m0));
   st_begin();
   Pf pf;   // first k-blocks of the next dense layer (crosses the select / expand phases)
   pf_issue<NT256>(pf, &kernarg0<muz_net_w>()->dyn.d3, LAT, LAT);
@@ -146,11 +199,17 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     if (valid) {
       const WalkEnd w = walk(T, L, rk, sa.D, [&](const Kid& k, int node, int depth) -> float {
         int sumv;
-        float pmax;
-        const float cq = completed_q(k, s_raw[row][node], sa, sumv, pmax);
+        float pmax = rpm, pp = rpp;
+        if (depth == 0 ? !ROOT_PP : !NODE_PP) {
+          pp = prior_probs(k.prior, k.ok, pmax);
+        } else if (depth != 0) {
+          pp = tree_ld(T.pp(g, node, ai));   // (beside the node's other six words: no dependent round trip)
+        }
+        const float cq = completed_q(k, pp, s_raw[row][node], sa, sumv);
         if (depth == 0) {
-          // gumbel_muzero_root_action_selection: score_considered + masked_argmax
-          const int cv = considered_visit(ncons, sa.S, sumv);
+          // gumbel_muzero_root_action_selection: score_considered + masked_argmax (sumv: this simulation's index)
+          // CV_TAB: the table's entry, passed through considered_visit (m = 0 returns the index at its first line)
+          const int cv = considered_visit(CV_TAB ? cv_m0 : ncons, sa.S, CV_TAB ? (int)s_cv[row][sumv] : sumv);
           const float s = fmaxf(-1e9f, gum + (k.prior - pmax) + cq) + (k.visits == cv ? 0.f : -INFINITY);
           return (!ok || ((lb >> a) & 1u) == 0u) ? -INFINITY : s;
         }
@@ -188,7 +247,13 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     if (valid) {
       // the new node keeps its prior logits
       const float v = ar.v0[row], rw = ar.v1[row], dc = ar.v2[row];
-      commit_expansion(T, L, rk, sim, ar.U[row * LD + ai], v, rw, dc);
+      const float prior = ar.U[row * LD + ai];
+      commit_expansion(T, L, rk, sim, prior, v, rw, dc);
+      if constexpr (NODE_PP) {   // ... and their prior_probs, for every later walk through it
+        float pm;
+        const float pp = prior_probs(prior, ok, pm);
+        if (ok) tree_st(T.pp(g, nx, a), pp);
+      }
       if (a == 0) s_raw[row][nx] = v;
       // ---------------- backward (search.py backward) along the recorded path
       commit_backup(T, L, rk, v, rw, dc);
@@ -209,8 +274,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   if (valid) {
     const Kid& k = rk;
     int sumv;
-    float pmax;
-    const float cq = completed_q(k, s_raw[row][0], sa, sumv, pmax);
+    float pmax = rpm, pp = rpp;
+    if constexpr (!ROOT_PP) pp = prior_probs(k.prior, k.ok, pmax);
+    const float cq = completed_q(k, pp, s_raw[row][0], sa, sumv);
     const bool inv = !ok || ((lb >> a) & 1u) == 0u;
     const int cv = row_imax(k.visits);   // considered_visit = max(visit_counts)
     float sc = fmaxf(-1e9f, gum + (k.prior - pmax) + cq) + (k.visits == cv ? 0.f : -INFINITY);
@@ -234,13 +300,31 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
 
 int64_t search_workspace_bytes(int n, int S) { return (int64_t)TreeWs::bytes(n, S + 1); }
 
+// MUZ_SELECT_INVARIANTS (read per launch): which of the select phase's invariants are evaluated once (see kSelDefault)
+static int select_form() {
+  const char* e = getenv("MUZ_SELECT_INVARIANTS");
+  return e ? atoi(e) : 1;
+}
+
 int launch_gumbel_search(const muz_net_w& w, const SearchArgs& sa, const float* root_logits, const float* root_value,
                          const float* root_emb, const uint32_t* legal, const float* gumbel, const int32_t* game_id,
                          int n, const int* n_dev, void* workspace, int32_t* action, float* weights, float* value,
                          hipStream_t s) {
-  const TreeWs T = TreeWs::carve(workspace, n, sa.S + 1);
-  k_gumbel_search<<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal,
-                                                               gumbel, game_id, n, n_dev, T, action, weights, value);
+  const GumbelTree T{TreeWs::carve(workspace, n, sa.S + 1)};
+  const dim3 grid((n + kRows - 1) / kRows);
+  switch (select_form()) {
+    case 0:
+      k_gumbel_search<0><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal, gumbel, game_id, n,
+                                                   n_dev, T, action, weights, value);
+      break;
+    case 2:
+      k_gumbel_search<kSelAll><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal, gumbel,
+                                                         game_id, n, n_dev, T, action, weights, value);
+      break;
+    default:
+      k_gumbel_search<kSelDefault><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal, gumbel,
+                                                             game_id, n, n_dev, T, action, weights, value);
+  }
   return muz_last_launch_error();
 }
 
@@ -268,6 +352,13 @@ int muz_gumbel_search(const muz_net_w* w, const muz_search_cfg* cfg, const float
   if (rc || n == 0) return rc;
   return launch_gumbel_search(*w, make_search_args(*cfg), root_logits, root_value, root_embedding, legal_bits, gumbel, game_id, n, nullptr,
                               workspace, action, action_weights, root_value_out, (hipStream_t)stream);
+}
+
+int muz_considered_visits(int32_t num_considered, int32_t num_simulations, uint8_t* out) {
+  if (!out || num_considered < 0) return MUZ_E_INVALID;
+  if (num_simulations < 1 || num_simulations > kMaxSims) return MUZ_E_UNSUPPORTED;
+  fill_considered_visits(out, num_considered, num_simulations, 0, 1);
+  return MUZ_OK;
 }
 
 #ifdef MUZ_STAMPS2

@@ -86,7 +86,7 @@ struct Kid {
 };
 
 // seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.
-__device__ __forceinline__ int considered_visit(int m, int S, int idx) {
+__host__ __device__ __forceinline__ int considered_visit(int m, int S, int idx) {
   if (m <= 1) return idx;
   int log2max = 0;
   while ((1 << log2max) < m) ++log2max;
@@ -102,10 +102,19 @@ __device__ __forceinline__ int considered_visit(int m, int S, int idx) {
   }
   return v;
 }
+// The same sequence as a table: entries first, first + step, ... of cv[0..S) (k_gumbel_search: the 32 lanes of a game
+// fill its LDS row once per search, lane i the entries i, i + 32, ...; the host entry fills all of it).  S <= kMaxSims,
+// so every value fits a byte.
+__host__ __device__ __forceinline__ void fill_considered_visits(uint8_t* cv, int m, int S, int first, int step) {
+  static_assert(kMaxSims <= 255, "considered-visit table entries are bytes");
+  for (int i = first; i < S; i += step) cv[i] = (uint8_t)considered_visit(m, S, i);
+}
 
 // A narrow tree's workspace: six children arrays [n][N][APAD] (a node's A <= APAD children padded to APAD), then the
 // node embeddings [n][N][256].  Arrays: TreeArrays, or a struct derived from it for a kernel that keeps further
-// per-node arrays after these (the kernel argument's layout is the arrays, then N).
+// per-node arrays after these (the kernel argument's layout is the arrays, then N).  The pad slots A..APAD-1 of a node
+// are read and written by nothing here; k_gumbel_search keeps a seventh per-child word in those of three of the float
+// arrays (search.hip GumbelTree), so the workspace and its cache lines stay what they are.
 struct TreeArrays {
   int32_t* c_index;
   float* c_prior;

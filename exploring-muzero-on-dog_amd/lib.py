@@ -368,6 +368,7 @@ SIGNATURES = {
     "muz_search_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),
     "muz_gumbel_search": (ctypes.c_int, [ctypes.POINTER(MuzNetW), ctypes.POINTER(MuzSearchCfg), vp, vp, vp, vp,
                                          vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "muz_considered_visits": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, vp]),
     "muz_puct_search": (ctypes.c_int, [ctypes.POINTER(MuzNetW), ctypes.POINTER(MuzPuctCfg), vp, vp, vp, vp, vp,
                                        vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
     "muz_selfplay_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),

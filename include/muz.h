@@ -409,6 +409,14 @@ int muz_gumbel_search(const muz_net_w* w /*host*/, const muz_search_cfg* cfg /*h
                       const float* gumbel, const int32_t* game_id, int32_t n, void* workspace,
                       int64_t workspace_bytes, int32_t* action, float* action_weights, float* root_value_out,
                       void* stream);
+/* Environment switch, read per launch (self-play's searches included): MUZ_SELECT_INVARIANTS chooses which of the
+ * select phase's invariants are evaluated once instead of at every walk level -- unset or 1: the root's prior softmax
+ * and its considered-visit sequence; 0: none; 2: also every node's prior softmax, kept in the tree.  The outputs do not
+ * change (A/B runs, tests). */
+
+/* Host only: seq_halving.get_sequence_of_considered_visits(num_considered, num_simulations) as the search tabulates it
+ * per game, out [num_simulations] (num_simulations 1..100: every entry fits a byte). */
+int muz_considered_visits(int32_t num_considered, int32_t num_simulations, uint8_t* out /*host*/);
 
 /* ---- PUCT MuZero search: the second policy of run_muzero_mcts (muzero_deterministic_madn.py:685-697, the
  * mctx.muzero_policy call the reference keeps commented beside the Gumbel one) -------------------------------
