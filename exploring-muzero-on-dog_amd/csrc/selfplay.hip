@@ -17,7 +17,6 @@
 #include "host_consts.hpp"
 #include "launch.hpp"
 #include "selfplay_host.hpp"
-#include "turn_ledger.hpp"
 
 namespace muz {
 
@@ -99,26 +98,6 @@ __global__ __launch_bounds__(kSpBlock) void k_sp_apply_g(DetConsts c, muz_detmad
   if (f) sp_apply_game<G>(c, sstate[lg], sboard[lg], f, slot[g], legal[g], gn, tt, s_action, s_weights, s_value, tr, a);
   __syncthreads();
   det_rows_store<NG>(c, st, g0, games, sboard, sstate, t, kSpBlock);
-}
-
-__device__ void det_reset_lane(const DetConsts& c, const muz_detmadn_soa& st, int g) {
-  const int S = st.stride;
-  const bool fp = has(c.flags, R_FREE_PIN);
-  for (int cell = 0; cell < kCells; ++cell) st.board[cell * S + g] = -1;
-  for (int p = 0; p < c.P; ++p) {
-    for (int k = 0; k < 4; ++k) st.pins[(p * 4 + k) * S + g] = (int8_t)((fp && k == 0) ? c.start[p] : -1);
-    for (int m = 0; m < 6; ++m) st.action_set[(p * 6 + m) * S + g] = 4;
-    if (fp) st.board[c.start[p] * S + g] = (int8_t)p;
-  }
-  st.current_player[g] = (int8_t)c.starting_player;
-  st.reward[g] = 0;
-  st.done[g] = 0;
-}
-
-__global__ void k_det_reset_sp(DetConsts c, muz_detmadn_soa st, int n) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n) return;
-  det_reset_lane(c, st, g);
 }
 
 // ---- the turn head as one launch: refill + flags + compaction + encode ------------------------------------------
@@ -246,7 +225,7 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
     }
     __syncthreads();
     if (t < games && s_f[t]) lane_game[g0 + t] = s_gn[t];
-    if (s_reset) {   // det_reset_lane on the LDS rows of the refilled lanes (stored back below)
+    if (s_reset) {   // DetGame::reset_lane on the LDS rows of the refilled lanes (stored back below)
       const bool fp = has(c.flags, R_FREE_PIN);
       for (int i = t; i < NG * kCells; i += kHeadBlock) {
         const int gi = i / kCells, cell = i % kCells;
@@ -381,14 +360,6 @@ __global__ __launch_bounds__(kHeadBlock) void k_sp_head(DetConsts c, muz_detmadn
   if (APPLY || (STREAM && (s_reset | s_ffwd))) det_rows_store<NG>(c, st, g0, games, sboard, sstate, t, kHeadBlock);
 }
 
-__global__ void k_ss_init(DetConsts c, muz_detmadn_soa st, int32_t* lane_game, int32_t* next, int num_games, int W) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l == 0) next[0] = min(num_games, W);
-  if (l >= W) return;
-  lane_game[l] = l < num_games ? l : -1;
-  det_reset_lane(c, st, l);
-}
-
 // The streaming driver's fast-forward cap: kSpFfCap unless MUZ_SP_FASTFORWARD says otherwise (read per call) --
 // 0 selects the head without fast-forward (A/B runs), 1 .. kSpFfCap that many no-move turns per game and launch
 // (tests of the cap path).
@@ -401,8 +372,10 @@ static int sp_fastforward_cap() {
 // device-resident row count) into the per-slot ws.action / ws.weights / ws.value, noise keyed by the game's number
 // (key_game = lane_game) and its own step count (key_turn = tr.idx, == the turn for every game of a batch).
 struct GumbelTurn {
+  using Cfg = muz_search_cfg;
+  static int check(const Cfg&) { return MUZ_OK; }
   SearchArgs sa;
-  GumbelTurn(const muz_search_cfg& cfg, const int32_t* lane_game, const int32_t* idx) : sa(make_search_args(cfg)) {
+  GumbelTurn(const Cfg& cfg, const int32_t* lane_game, const int32_t* idx) : sa(make_search_args(cfg)) {
     sa.key_turn = idx;
     sa.key_game = lane_game;
   }
@@ -413,10 +386,13 @@ struct GumbelTurn {
   }
 };
 // muzero_policy (puct_search.hip) on the same tree workspace; Dirichlet, tie-break and final-draw noise from the
-// counter RNG (cfg.turn is not used: key_turn is set for both drivers)
+// counter RNG (cfg.turn is not used: key_turn is set for both drivers); the policy's own settings are refused as its
+// search entry point refuses them
 struct PuctTurn {
+  using Cfg = muz_puct_cfg;
+  static int check(const Cfg& cfg) { return check_puct_cfg(cfg); }
   PuctArgs pa;
-  PuctTurn(const muz_puct_cfg& cfg, const int32_t* lane_game, const int32_t* idx) : pa(make_puct_args(cfg)) {
+  PuctTurn(const Cfg& cfg, const int32_t* lane_game, const int32_t* idx) : pa(make_puct_args(cfg)) {
     pa.key_turn = idx;
     pa.key_game = lane_game;
   }
@@ -426,27 +402,57 @@ struct PuctTurn {
                               n, counts, ws.tree, ws.action, ws.weights, ws.value, s);
   }
 };
-static int check_policy_cfg(const muz_search_cfg&) { return MUZ_OK; }
-static int check_policy_cfg(const muz_puct_cfg& cfg) { return check_puct_cfg(cfg); }
 
-// The turn loop shared by the batch and the streaming driver.  Batch: lane g plays game g for at most T
-// turns.  Streaming (lane_game != null): lanes are refilled with the next game number when theirs ends,
-// until num_games games have been played.  Search: GumbelTurn or PuctTurn.
+// Det MADN as the turn loop plays it (selfplay_host.hpp: sp_turns), with Search = GumbelTurn or PuctTurn.  The head is
+// one launch, k_sp_head, which first applies the previous turn's searched actions: after_search only marks them
+// pending, and finish() applies the last turn's.
 template <class Search>
-static int sp_turns(const DetConsts& c, const muz_net_w* w, Search search, muz_detmadn_soa st, muz_traj tr,
-                    int n, const SpWs& ws, const int32_t* lane_game, int num_games, int max_turns, int ff_cap,
-                    muz_sp_stats* stats, hipStream_t s) {
-  const int T = tr.max_steps;
-  int rc = MUZ_OK;
+struct DetGame {
+  using Net = muz_net_w;
+  using Cfg = typename Search::Cfg;
+  using Soa = muz_detmadn_soa;
+  using Records = muz_traj;
+  static int check(const Net* w, const Cfg* cfg, int P) {
+    if (!w || !cfg) return MUZ_E_INVALID;
+    if (w->obs_channels != 8 * P + 2 || w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
+    return Search::check(*cfg);
+  }
+  // (the head writes the observation records and its workspace in 16-byte chunks)
+  static bool args_ok(int lanes, int num_games, int stride, const void* workspace, const Records& tr) {
+    return sp_args_ok(lanes, num_games, stride, workspace, tr, true);
+  }
+  static size_t carve(char* base, int n, int C, int S, SpWs* ws) {
+    return sp_carve(base, n, C, MUZ_DET_ACTIONS, (size_t)search_workspace_bytes(n, S), ws);
+  }
+  // zeroed records, and both parities of k_sp_head's counters
+  static int clear(const Records& tr, int games, int C, const SpWs& ws, hipStream_t s) {
+    MUZ_HIP_RET(hipMemsetAsync(ws.counts, 0, 8 * sizeof(int32_t), s));
+    return traj_clear(tr, games, C, MUZ_DET_ACTIONS, s);
+  }
+  static __device__ void reset_lane(const DetConsts& c, const Soa& st, int g) {
+    madn_reset_lane(c, st, g);
+    for (int r = 0; r < 6 * c.P; ++r) st.action_set[r * st.stride + g] = 4;
+  }
 
-  TurnLedger led(s, stats != nullptr);
-  if ((rc = led.begin())) return rc;
-  MUZ_HIP_RET(hipMemsetAsync(ws.counts, 0, 8 * sizeof(int32_t), s));   // both parities of k_sp_head's counters
-  int turns = 0;
-  bool pending = false;   // a turn's searched actions not applied yet
-  rc = MUZ_OK;
-  for (int turn = 0; turn < max_turns; ++turn) {
-    if (!led.proceed(turn)) break;
+  const DetConsts& c;
+  const Net& w;
+  Soa st;
+  muz_traj tr;
+  int n;
+  const SpWs& ws;
+  const int32_t* lane_game;   // streaming: the game number of every lane; batch: null, lane g plays game g
+  int num_games, ff_cap;
+  hipStream_t s;
+  Search search_;
+  bool pending = false;       // a turn's searched actions not applied yet
+
+  DetGame(const DetConsts& c, const Net& w, const Cfg& cfg, Soa st, const Records& tr, int n, const SpWs& ws,
+          bool stream, int num_games, hipStream_t s)
+      : c(c), w(w), st(st), tr(tr), n(n), ws(ws), lane_game(stream ? ws.lane_game : nullptr), num_games(num_games),
+        ff_cap(stream ? sp_fastforward_cap() : 0), s(s), search_(cfg, lane_game, tr.idx) {}
+
+  TurnCounts head(int turn, TurnLedger& led) {
+    const int T = tr.max_steps;
     const int nbh = (n + kHeadBlock / kFlagLanes - 1) / (kHeadBlock / kFlagLanes);
     int32_t* const counts = ws.counts + 4 * (turn & 1);   // (the other parity: the next turn's, zeroed by the head)
     // (the ledger's counts reach the host through root inference's first kernel: no last-arrival ticket here)
@@ -466,79 +472,21 @@ static int sp_turns(const DetConsts& c, const muz_net_w* w, Search search, muz_d
     }
     pending = false;
     if (!host_counts) led.counts(turn, counts);
-    if ((rc = muz_last_launch_error())) break;
-    if ((rc = launch_root_inference(*w, ws.obs, n, counts, ws.conv, ws.root_logits, ws.root_value, ws.root_emb,
-                                    s, host_counts)))
-      break;
-    if (host_counts) led.counts_written(turn);
-    led.search_begin(turn);
-    if ((rc = search(*w, ws, n, counts, turn, s))) break;
-    led.search_end(turn);
-    pending = true;   // applied by the next turn's head (or after the loop)
-    if ((rc = muz_last_launch_error())) break;
-    ++turns;
+    return {counts, host_counts};
   }
-  if (pending && rc == MUZ_OK) {   // the last launched turn's apply
+  int root(const TurnCounts& tc) {
+    return launch_root_inference(w, ws.obs, n, tc.dev, ws.conv, ws.root_logits, ws.root_value, ws.root_emb, s,
+                                 tc.host_slot);
+  }
+  int search(const int32_t* counts, int turn) { return search_(w, ws, n, counts, turn, s); }
+  void after_search(int) { pending = true; }   // applied by the next turn's head, or by finish()
+  int finish() {
+    if (!pending) return MUZ_OK;
     k_sp_apply_g<<<(n + kSpBlock / kFlagLanes - 1) / (kSpBlock / kFlagLanes), kSpBlock, 0, s>>>(
         c, st, ws.flag, ws.slot, ws.action, ws.weights, ws.value, tr, n, lane_game, ws.legal);
-    rc = muz_last_launch_error();
+    return muz_last_launch_error();
   }
-  led.finish(turns, stats);
-  return rc;
-}
-
-static size_t det_carve(char* base, int n, int C, int S, SpWs* ws) {
-  return sp_carve(base, n, C, MUZ_DET_ACTIONS, (size_t)search_workspace_bytes(n, S), ws);
-}
-
-// The checks of every entry point (`lanes` games at a time out of num_games; Cfg: muz_search_cfg or muz_puct_cfg, the
-// policy's own settings refused as its search entry point refuses them), then the carve
-template <class Cfg>
-static int sp_setup(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, const muz_detmadn_soa& st,
-                    const muz_traj& tr, int lanes, int num_games, void* workspace, int64_t workspace_bytes,
-                    muz_sp_stats* stats, DetConsts* c, SpWs* ws) {
-  int rc = make_det_consts(rules, c);
-  if (rc) return rc;
-  if (!w || !cfg) return MUZ_E_INVALID;
-  if (w->obs_channels != 8 * c->P + 2 || w->num_actions != MUZ_DET_ACTIONS) return MUZ_E_UNSUPPORTED;
-  if ((rc = check_policy_cfg(*cfg))) return rc;
-  MUZ_HOST_CHECK(sp_args_ok(lanes, num_games, st.stride, workspace, tr, true));
-  if ((rc = check_search_limits(cfg->num_simulations, cfg->max_depth))) return rc;
-  if (stats) *stats = muz_sp_stats{};
-  MUZ_HOST_CHECK(workspace_bytes >= (int64_t)det_carve(nullptr, lanes, w->obs_channels, cfg->num_simulations, nullptr));
-  det_carve((char*)workspace, lanes, w->obs_channels, cfg->num_simulations, ws);
-  return MUZ_OK;
-}
-
-// play_n_games_v3 with either search: batch_reset + zeroed buffers, then the turn loop
-template <class Search, class Cfg>
-static int sp_batch(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, muz_detmadn_soa st, muz_traj tr, int n,
-                    void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, hipStream_t s) {
-  DetConsts c;
-  SpWs ws;
-  int rc = sp_setup(rules, w, cfg, st, tr, n, n, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0) return rc;
-  k_det_reset_sp<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
-  if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
-  return sp_turns(c, w, Search(*cfg, nullptr, tr.idx), st, tr, n, ws, nullptr, n, tr.max_steps, 0, stats, s);
-}
-
-template <class Search, class Cfg>
-static int sp_stream(const muz_rules* rules, const muz_net_w* w, const Cfg* cfg, muz_detmadn_soa st, muz_traj tr,
-                     int num_games, int lanes, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
-                     hipStream_t s) {
-  DetConsts c;
-  SpWs ws;
-  const int n = lanes;
-  int rc = sp_setup(rules, w, cfg, st, tr, n, num_games, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0 || num_games == 0) return rc;
-  if ((rc = traj_clear(tr, num_games, w->obs_channels, MUZ_DET_ACTIONS, s))) return rc;
-  // lane l starts game l (l < num_games); later games are handed out by the turn head's refill
-  k_ss_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
-  MUZ_HIP_RET(hipGetLastError());
-  return sp_turns(c, w, Search(*cfg, ws.lane_game, tr.idx), st, tr, n, ws, ws.lane_game, num_games,
-                  stream_max_turns(num_games, n, tr.max_steps), sp_fastforward_cap(), stats, s);
-}
+};
 
 }  // namespace muz
 
@@ -548,33 +496,35 @@ extern "C" {
 
 int64_t muz_selfplay_workspace_bytes(int32_t n, int32_t obs_channels, const muz_search_cfg* cfg) {
   if (!cfg || n < 0) return -1;
-  return (int64_t)det_carve(nullptr, n, obs_channels, cfg->num_simulations, nullptr);
+  return (int64_t)DetGame<GumbelTurn>::carve(nullptr, n, obs_channels, cfg->num_simulations, nullptr);
 }
 
 int muz_detmadn_selfplay(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg, muz_detmadn_soa st,
                          muz_traj tr, int32_t n, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
                          void* stream) {
-  return sp_batch<GumbelTurn>(rules, w, cfg, st, tr, n, workspace, workspace_bytes, stats, (hipStream_t)stream);
+  return sp_play<DetGame<GumbelTurn>>(rules, w, cfg, st, tr, n, n, false, workspace, workspace_bytes, stats,
+                                      (hipStream_t)stream);
 }
 
 int muz_detmadn_selfplay_stream(const muz_rules* rules, const muz_net_w* w, const muz_search_cfg* cfg,
                                 muz_detmadn_soa st, muz_traj tr, int32_t num_games, int32_t lanes, void* workspace,
                                 int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
-  return sp_stream<GumbelTurn>(rules, w, cfg, st, tr, num_games, lanes, workspace, workspace_bytes, stats,
-                               (hipStream_t)stream);
+  return sp_play<DetGame<GumbelTurn>>(rules, w, cfg, st, tr, num_games, lanes, true, workspace, workspace_bytes, stats,
+                                      (hipStream_t)stream);
 }
 
 int muz_detmadn_selfplay_puct(const muz_rules* rules, const muz_net_w* w, const muz_puct_cfg* cfg, muz_detmadn_soa st,
                               muz_traj tr, int32_t n, void* workspace, int64_t workspace_bytes, muz_sp_stats* stats,
                               void* stream) {
-  return sp_batch<PuctTurn>(rules, w, cfg, st, tr, n, workspace, workspace_bytes, stats, (hipStream_t)stream);
+  return sp_play<DetGame<PuctTurn>>(rules, w, cfg, st, tr, n, n, false, workspace, workspace_bytes, stats,
+                                    (hipStream_t)stream);
 }
 
 int muz_detmadn_selfplay_puct_stream(const muz_rules* rules, const muz_net_w* w, const muz_puct_cfg* cfg,
                                      muz_detmadn_soa st, muz_traj tr, int32_t num_games, int32_t lanes,
                                      void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
-  return sp_stream<PuctTurn>(rules, w, cfg, st, tr, num_games, lanes, workspace, workspace_bytes, stats,
-                             (hipStream_t)stream);
+  return sp_play<DetGame<PuctTurn>>(rules, w, cfg, st, tr, num_games, lanes, true, workspace, workspace_bytes, stats,
+                                    (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -11,7 +11,6 @@
 #include "launch.hpp"
 #include "rng.hpp"
 #include "selfplay_host.hpp"
-#include "turn_ledger.hpp"
 
 namespace muz {
 
@@ -141,31 +140,8 @@ __global__ __launch_bounds__(kCsBlock) void k_cs_apply(DetConsts c, muz_classic_
 }
 
 __device__ void cls_reset_lane(const DetConsts& c, const muz_classic_soa& st, int g) {
-  const int S = st.stride;
-  const bool fp = has(c.flags, R_FREE_PIN);
-  for (int cell = 0; cell < kCells; ++cell) st.board[cell * S + g] = -1;
-  for (int p = 0; p < c.P; ++p) {
-    for (int k = 0; k < 4; ++k) st.pins[(p * 4 + k) * S + g] = (int8_t)((fp && k == 0) ? c.start[p] : -1);
-    if (fp) st.board[c.start[p] * S + g] = (int8_t)p;
-  }
-  st.current_player[g] = (int8_t)c.starting_player;
-  st.reward[g] = 0;
-  st.done[g] = 0;
+  madn_reset_lane(c, st, g);
   st.die[g] = 0;
-}
-
-__global__ void k_cs_reset(DetConsts c, muz_classic_soa st, int n) {
-  const int g = blockIdx.x * blockDim.x + threadIdx.x;
-  if (g >= n) return;
-  cls_reset_lane(c, st, g);
-}
-
-__global__ void k_cs_init(DetConsts c, muz_classic_soa st, int32_t* lane_game, int32_t* next, int num_games, int W) {
-  const int l = blockIdx.x * blockDim.x + threadIdx.x;
-  if (l == 0) next[0] = min(num_games, W);
-  if (l >= W) return;
-  lane_game[l] = l < num_games ? l : -1;
-  cls_reset_lane(c, st, l);
 }
 
 // Streaming refill (one workgroup, deterministic): every lane whose game ended (done, or its record is full) takes
@@ -208,68 +184,88 @@ __global__ __launch_bounds__(kScanThreads) void k_cs_refill(DetConsts c, muz_cla
   if (t == kScanThreads - 1) next[0] = min(num_games, base + part[t]);
 }
 
-// Turn loop shared by the batch and the streaming driver (see selfplay.hip sp_turns).
-static int cs_turns(const DetConsts& c, const muz_classic_net_w* w, const muz_stoch_cfg* cfg, muz_classic_soa st,
-                    muz_traj tr, muz_traj_chance ch, int n, const SpWs& ws, const int32_t* lane_game, int num_games,
-                    int max_turns, muz_sp_stats* stats, hipStream_t s) {
-  const int T = tr.max_steps;
-  int rc = MUZ_OK;
-  SArgs sa = make_sargs(*cfg, w->num_actions);
-  sa.key_game = lane_game;
-  sa.key_turn = tr.idx;   // the game's own step count (== the turn for every game of a batch)
-  TurnLedger led(s, stats != nullptr);
-  if ((rc = led.begin())) return rc;
-  int turns = 0;
-  rc = MUZ_OK;
-  for (int turn = 0; turn < max_turns; ++turn) {
-    if (!led.proceed(turn)) break;
+// The turn's search as sp_turns launches it (see GumbelTurn, selfplay.hip)
+struct StochasticTurn {
+  SArgs sa;
+  StochasticTurn(const muz_stoch_cfg& cfg, const int32_t* lane_game, const int32_t* idx)
+      : sa(make_sargs(cfg, MUZ_CLASSIC_ACTIONS)) {
+    sa.key_game = lane_game;
+    sa.key_turn = idx;   // the game's own step count (== the turn for every game of a batch)
+  }
+  int operator()(const muz_classic_net_w& w, const SpWs& ws, int n, const int* counts, int turn, hipStream_t s) {
+    sa.turn = turn;
+    return launch_stochastic_search(w, sa, ws.root_logits, ws.root_value, ws.root_emb, ws.legal_c, nullptr, nullptr,
+                                    ws.list, n, counts, ws.tree, ws.action, ws.weights, ws.value, s);
+  }
+};
+
+// The records of a classic game: the det keys and, beside them, the die and the next state's dice distribution
+struct ClassicRecords : muz_traj {
+  muz_traj_chance ch;
+};
+
+// Classic MADN as the turn loop plays it (selfplay_host.hpp: sp_turns): the head is four launches (refill, flags,
+// compaction, encode) and the apply follows the search within the turn.
+struct ClassicGame {
+  using Net = muz_classic_net_w;
+  using Cfg = muz_stoch_cfg;
+  using Soa = muz_classic_soa;
+  using Records = ClassicRecords;
+  static int check(const Net* w, const Cfg* cfg, int P) {
+    if (!cfg) return MUZ_E_INVALID;
+    if (int rc = check_classic_net(w)) return rc;
+    return w->obs_channels == 2 * P + 3 ? MUZ_OK : MUZ_E_UNSUPPORTED;
+  }
+  static bool args_ok(int lanes, int num_games, int stride, const void* workspace, const Records& rec) {
+    return sp_args_ok(lanes, num_games, stride, workspace, rec, false) && rec.ch.dice && rec.ch.dice_dist;
+  }
+  static size_t carve(char* base, int n, int C, int S, SpWs* ws) {
+    return sp_carve(base, n, C, MUZ_CLASSIC_ACTIONS, (size_t)stochastic_workspace_bytes(n, S), ws);
+  }
+  static int clear(const Records& rec, int games, int C, const SpWs&, hipStream_t s) {
+    if (int rc = traj_clear(rec, games, C, MUZ_CLASSIC_ACTIONS, s)) return rc;
+    return traj_clear(rec.ch, games, rec.max_steps, s);
+  }
+  static __device__ void reset_lane(const DetConsts& c, const Soa& st, int g) { cls_reset_lane(c, st, g); }
+
+  const DetConsts& c;
+  const Net& w;
+  Soa st;
+  Records tr;   // (with tr.ch, the chance records)
+  int n;
+  const SpWs& ws;
+  const int32_t* lane_game;   // streaming: the game number of every lane; batch: null, lane g plays game g
+  int num_games;
+  unsigned long long seed;
+  hipStream_t s;
+  StochasticTurn search_;
+
+  ClassicGame(const DetConsts& c, const Net& w, const Cfg& cfg, Soa st, const Records& rec, int n, const SpWs& ws,
+              bool stream, int num_games, hipStream_t s)
+      : c(c), w(w), st(st), tr(rec), n(n), ws(ws), lane_game(stream ? ws.lane_game : nullptr),
+        num_games(num_games), seed(cfg.seed), s(s), search_(cfg, lane_game, tr.idx) {}
+
+  TurnCounts head(int turn, TurnLedger& led) {
+    const int T = tr.max_steps;
     if (lane_game)
       k_cs_refill<<<1, kScanThreads, 0, s>>>(c, st, ws.lane_game, tr.idx, T, ws.next_game, num_games, n);
-    k_cs_flags<<<(n + kCsBlock - 1) / kCsBlock, kCsBlock, 0, s>>>(c, st, cfg->seed, tr.idx, T, lane_game, ws.legal,
+    k_cs_flags<<<(n + kCsBlock - 1) / kCsBlock, kCsBlock, 0, s>>>(c, st, seed, tr.idx, T, lane_game, ws.legal,
                                                                    ws.flag, n);
     k_sp_compact<<<1, kScanThreads, 0, s>>>(ws.flag, n, ws.list, ws.slot, ws.counts);
     led.counts(turn, ws.counts);
     k_cs_encode<<<n, 64, 0, s>>>(c, st, ws.list, ws.counts, ws.legal, ws.legal_c, ws.obs, tr.obs, tr.idx, T, lane_game);
-    if ((rc = muz_last_launch_error())) break;
-    if ((rc = launch_root_inference(*w, ws.obs, n, ws.counts, ws.conv, ws.root_logits, ws.root_value, ws.root_emb,
-                                    s)))
-      break;
-    sa.turn = turn;
-    led.search_begin(turn);
-    if ((rc = launch_stochastic_search(*w, sa, ws.root_logits, ws.root_value, ws.root_emb, ws.legal_c, nullptr, nullptr,
-                                       ws.list, n, ws.counts, ws.tree, ws.action, ws.weights, ws.value, s)))
-      break;
-    led.search_end(turn);
-    k_cs_apply<<<(n + kCsBlock - 1) / kCsBlock, kCsBlock, 0, s>>>(c, st, ws.flag, ws.slot, ws.action, ws.weights,
-                                                                   ws.value, tr, ch, n, lane_game, ws.legal);
-    if ((rc = muz_last_launch_error())) break;
-    ++turns;
+    return {ws.counts, nullptr};
   }
-  led.finish(turns, stats);
-  return rc;
-}
-
-
-static size_t cs_carve(char* base, int n, int C, int S, SpWs* ws) {
-  return sp_carve(base, n, C, MUZ_CLASSIC_ACTIONS, (size_t)stochastic_workspace_bytes(n, S), ws);
-}
-
-// The checks of both entry points (`lanes` games at a time out of num_games), then the carve
-static int cs_setup(const muz_rules* rules, const muz_classic_net_w* w, const muz_stoch_cfg* cfg,
-                    const muz_classic_soa& st, const muz_traj& tr, const muz_traj_chance& ch, int lanes, int num_games,
-                    void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, DetConsts* c, SpWs* ws) {
-  int rc = make_det_consts(rules, c);
-  if (rc) return rc;
-  if (!cfg) return MUZ_E_INVALID;
-  if ((rc = check_classic_net(w))) return rc;
-  if (w->obs_channels != 2 * c->P + 3) return MUZ_E_UNSUPPORTED;
-  MUZ_HOST_CHECK(sp_args_ok(lanes, num_games, st.stride, workspace, tr, false) && ch.dice && ch.dice_dist);
-  if ((rc = check_search_limits(cfg->num_simulations, cfg->max_depth))) return rc;
-  if (stats) *stats = muz_sp_stats{};
-  MUZ_HOST_CHECK(workspace_bytes >= (int64_t)cs_carve(nullptr, lanes, w->obs_channels, cfg->num_simulations, nullptr));
-  cs_carve((char*)workspace, lanes, w->obs_channels, cfg->num_simulations, ws);
-  return MUZ_OK;
-}
+  int root(const TurnCounts& tc) {
+    return launch_root_inference(w, ws.obs, n, tc.dev, ws.conv, ws.root_logits, ws.root_value, ws.root_emb, s);
+  }
+  int search(const int32_t* counts, int turn) { return search_(w, ws, n, counts, turn, s); }
+  void after_search(int) {
+    k_cs_apply<<<(n + kCsBlock - 1) / kCsBlock, kCsBlock, 0, s>>>(c, st, ws.flag, ws.slot, ws.action, ws.weights,
+                                                                   ws.value, tr, tr.ch, n, lane_game, ws.legal);
+  }
+  int finish() { return MUZ_OK; }
+};
 
 }  // namespace muz
 
@@ -279,38 +275,21 @@ extern "C" {
 
 int64_t muz_classic_selfplay_workspace_bytes(int32_t n, int32_t obs_channels, const muz_stoch_cfg* cfg) {
   if (!cfg || n < 0 || cfg->num_simulations < 1) return -1;
-  return (int64_t)cs_carve(nullptr, n, obs_channels, cfg->num_simulations, nullptr);
+  return (int64_t)ClassicGame::carve(nullptr, n, obs_channels, cfg->num_simulations, nullptr);
 }
 
 int muz_classic_selfplay(const muz_rules* rules, const muz_classic_net_w* w, const muz_stoch_cfg* cfg,
                          muz_classic_soa st, muz_traj tr, muz_traj_chance ch, int32_t n, void* workspace,
                          int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
-  DetConsts c;
-  SpWs ws;
-  int rc = cs_setup(rules, w, cfg, st, tr, ch, n, n, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  k_cs_reset<<<(n + 255) / 256, 256, 0, s>>>(c, st, n);
-  if ((rc = traj_clear(tr, n, w->obs_channels, MUZ_CLASSIC_ACTIONS, s))) return rc;
-  if ((rc = traj_clear(ch, n, tr.max_steps, s))) return rc;
-  return cs_turns(c, w, cfg, st, tr, ch, n, ws, nullptr, n, tr.max_steps, stats, s);
+  return sp_play<ClassicGame>(rules, w, cfg, st, {tr, ch}, n, n, false, workspace, workspace_bytes, stats,
+                              (hipStream_t)stream);
 }
 
 int muz_classic_selfplay_stream(const muz_rules* rules, const muz_classic_net_w* w, const muz_stoch_cfg* cfg,
                                 muz_classic_soa st, muz_traj tr, muz_traj_chance ch, int32_t num_games, int32_t lanes,
                                 void* workspace, int64_t workspace_bytes, muz_sp_stats* stats, void* stream) {
-  DetConsts c;
-  SpWs ws;
-  const int n = lanes;
-  int rc = cs_setup(rules, w, cfg, st, tr, ch, n, num_games, workspace, workspace_bytes, stats, &c, &ws);
-  if (rc || n == 0 || num_games == 0) return rc;
-  hipStream_t s = (hipStream_t)stream;
-  if ((rc = traj_clear(tr, num_games, w->obs_channels, MUZ_CLASSIC_ACTIONS, s))) return rc;
-  if ((rc = traj_clear(ch, num_games, tr.max_steps, s))) return rc;
-  k_cs_init<<<(n + 255) / 256, 256, 0, s>>>(c, st, ws.lane_game, ws.next_game, num_games, n);
-  MUZ_HIP_RET(hipGetLastError());
-  return cs_turns(c, w, cfg, st, tr, ch, n, ws, ws.lane_game, num_games, stream_max_turns(num_games, n, tr.max_steps),
-                  stats, s);
+  return sp_play<ClassicGame>(rules, w, cfg, st, {tr, ch}, num_games, lanes, true, workspace, workspace_bytes, stats,
+                              (hipStream_t)stream);
 }
 
 }  // extern "C"

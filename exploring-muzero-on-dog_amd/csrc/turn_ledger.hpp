@@ -1,4 +1,5 @@
-// Host-side bookkeeping of the native self-play turn loops (selfplay.hip, selfplay_classic.hip).
+// Host-side bookkeeping of the native self-play turn loop (sp_turns, selfplay_host.hpp), which owns it; a game's turn
+// head only says how the turn's counts reach it (counts, or device_slot for a kernel that writes them).
 //
 // Each turn copies its counts (games searching, games active at the start) into a small pinned ring and
 // records an event; the host reads a turn's counts kLag turns late, so the GPU queue never drains.  The

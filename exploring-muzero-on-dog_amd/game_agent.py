@@ -9,14 +9,13 @@ host<->device copy inside a turn.  ``obs`` is int8 (values 0..4); the reference 
 """
 from __future__ import annotations
 
-import ctypes
-
 import torch
 
 from . import detmadn as E
 from . import lib as _L
 from . import mcts as M
 from . import nets as N
+from .records import REFERENCE_DTYPES, NativeSelfPlay, as_traj, cached, reference_buffers  # noqa: F401 (re-exported)
 
 # MuZero_det_MADN/game_agent.py:12-22
 RULES = dict(E.SELFPLAY_RULES)
@@ -37,7 +36,7 @@ def check_policy(policy, policy_kwargs) -> dict:
     return kw
 
 
-class SelfPlayEngine:
+class SelfPlayEngine(NativeSelfPlay):
     """Owns the device state, trajectory buffers and workspace for repeated self-play calls."""
 
     def __init__(self, net: N.DeviceNet, num_envs: int, num_players: int = 4, max_steps: int = 550,
@@ -56,33 +55,7 @@ class SelfPlayEngine:
         r = dict(RULES if rules is None else rules)
         self.rules = E.make_rules(self.P, starting_player=starting_player, **r)
         self.state = E._alloc(self.n, self.P, self.rules, device)
-        n, T, A = self.n, self.T, net.A
-        z = dict(device=device)
-        self.buffers = {
-            "obs": torch.empty((n, T, self.C, E.CELLS), dtype=torch.int8, **z),
-            "act": torch.empty((n, T), dtype=torch.int32, **z),
-            "rew": torch.empty((n, T), dtype=torch.int32, **z),
-            "val": torch.empty((n, T), dtype=torch.float32, **z),
-            "pol": torch.empty((n, T, A), dtype=torch.float32, **z),
-            "mask": torch.empty((n, T), dtype=torch.float32, **z),
-            "player": torch.empty((n, T), dtype=torch.int32, **z),
-            "team": torch.empty((n, T), dtype=torch.int32, **z),
-            "discount": torch.empty((n, T), dtype=torch.int32, **z),
-            "idx": torch.empty((n,), dtype=torch.int32, **z),
-        }
-        lib = _L.load()
-        cfg = M.make_cfg(self.S, self.D)
-        nbytes = lib.muz_selfplay_workspace_bytes(n, self.C, cfg)
-        self.workspace = torch.empty((nbytes,), dtype=torch.uint8, **z)
-        self.last_turns = 0
-        self.last_stats = None
-
-    def traj(self) -> _L.MuzTraj:
-        t = _L.MuzTraj()
-        for k in ("obs", "act", "rew", "val", "pol", "mask", "player", "team", "discount", "idx"):
-            setattr(t, k, self.buffers[k].data_ptr())
-        t.max_steps = self.T
-        return t
+        self._alloc(net.A, _L.load().muz_selfplay_workspace_bytes(self.n, self.C, M.make_cfg(self.S, self.D)), device)
 
     def _search(self, seed, temperature):
         """-> (the call's search configuration, the batch entry point's name, the streaming one's)."""
@@ -95,17 +68,9 @@ class SelfPlayEngine:
     def play(self, seed: int, temperature: float = 1.0, stream=None, timing: bool = True) -> dict:
         """One play_n_games_v3 call.  The native loop synchronises its stream before returning.
         With ``timing`` the search launches are bracketed by HIP events (see ``last_stats``)."""
-        lib = _L.load()
         cfg, name, _ = self._search(seed, temperature)
-        st = _L.MuzSpStats()
-        _L.check(getattr(lib, name)(self.rules, self.net.w, cfg, self.state.soa(), self.traj(), self.n,
-                                    _L.ptr(self.workspace), _L.nbytes(self.workspace),
-                                    ctypes.byref(st) if timing else None, _L.stream_ptr(stream)), name)
-        self.last_stats = {"turns": st.turns, "searches": st.searches, "search_ms": st.search_ms,
-                           "total_ms": st.total_ms} if timing else None
-        self.last_turns = st.turns if timing else -1
+        self._call(name, cfg, self.traj(), None, (self.n,), stream, timing)
         return self.buffers
-
 
     def play_stream(self, num_games: int, seed: int, temperature: float = 1.0, stream=None,
                     timing: bool = True) -> dict:
@@ -113,26 +78,10 @@ class SelfPlayEngine:
         lane whose game ends starts the next one, so every search runs on a full batch until the last
         games.  Game k's trajectory equals game k of ``play`` on a batch of ``num_games``.  Returns
         buffers shaped [num_games, max_steps, ...] (reused across calls of the same size)."""
-        lib = _L.load()
-        num_games = int(num_games)
-        if getattr(self, "_sbuf_n", None) != num_games:
-            z = dict(device=self.buffers["act"].device)
-            self._sbuf = {k: torch.empty((num_games,) + tuple(v.shape[1:]), dtype=v.dtype, **z)
-                          for k, v in self.buffers.items()}
-            self._sbuf_n = num_games
-        t = _L.MuzTraj()
-        for k in ("obs", "act", "rew", "val", "pol", "mask", "player", "team", "discount", "idx"):
-            setattr(t, k, self._sbuf[k].data_ptr())
-        t.max_steps = self.T
+        buf = self._stream_buffers(int(num_games))
         cfg, _, name = self._search(seed, temperature)
-        st = _L.MuzSpStats()
-        _L.check(getattr(lib, name)(self.rules, self.net.w, cfg, self.state.soa(), t, num_games, self.n,
-                                    _L.ptr(self.workspace), _L.nbytes(self.workspace),
-                                    ctypes.byref(st) if timing else None, _L.stream_ptr(stream)), name)
-        self.last_stats = {"turns": st.turns, "searches": st.searches, "search_ms": st.search_ms,
-                           "total_ms": st.total_ms} if timing else None
-        self.last_turns = st.turns if timing else -1
-        return self._sbuf
+        self._call(name, cfg, as_traj(buf, self.T), None, (int(num_games), self.n), stream, timing)
+        return buf
 
 
 _ENGINE_CACHE = {}
@@ -141,39 +90,12 @@ _ENGINE_CACHE = {}
 def cached_engine(net: N.DeviceNet, num_envs, num_players, max_steps, num_simulation, max_depth, rules,
                   policy="gumbel", policy_kwargs=None) -> SelfPlayEngine:
     """The engine of the last reference-signature call, reused when the call's shape, rules, search policy (and its
-    keywords) and weight set are the same: a test_training-style loop calls play_n_games_v3 once per iteration, and a fresh engine would
-    reallocate its state, workspace and [num_envs, max_steps] buffers (GBs at config (e)) every time.  One live
-    engine per process (the reference's loops play one configuration at a time)."""
+    keywords) and weight set are the same (records.cached)."""
     kw = check_policy(policy, policy_kwargs)
     key = (id(net), int(num_envs), int(num_players), int(max_steps), int(num_simulation), int(max_depth),
            tuple(sorted((dict(RULES if rules is None else rules)).items())), policy, tuple(sorted(kw.items())))
-    hit = _ENGINE_CACHE.get(key)
-    if hit is not None and hit.net is net:
-        return hit
-    _ENGINE_CACHE.clear()
-    eng = _ENGINE_CACHE[key] = SelfPlayEngine(net, num_envs, num_players, max_steps, num_simulation, max_depth, rules,
-                                              policy=policy, policy_kwargs=kw)
-    return eng
-
-
-REFERENCE_DTYPES = {"obs": torch.float32, "act": torch.int32, "rew": torch.int32, "val": torch.float32,
-                    "pol": torch.float32, "mask": torch.float32, "player": torch.int32, "team": torch.int32,
-                    "discount": torch.int32, "idx": torch.int32}
-
-
-def reference_buffers(buf: dict, dtypes: dict) -> dict:
-    """Fresh copies of the engine's (reused) record buffers in the reference dtypes, with every row at or past a
-    game's ``idx`` as the reference's initial buffers hold it: zeros, ``team`` -1 (game_agent.py:158-169,
-    game_agent_stochastic.py:191-204).  The native loops write only rows below ``idx``."""
-    idx = buf["idx"].long()
-    past = torch.arange(buf["act"].shape[1], device=idx.device)[None, :] >= idx[:, None]
-    out = {}
-    for k, v in buf.items():
-        x = v.to(dtypes[k], copy=True)
-        if k != "idx":
-            x.masked_fill_(past.view(past.shape + (1,) * (x.dim() - 2)), -1 if k == "team" else 0)
-        out[k] = x
-    return out
+    return cached(_ENGINE_CACHE, key, net, lambda: SelfPlayEngine(net, num_envs, num_players, max_steps, num_simulation,
+                                                                  max_depth, rules, policy=policy, policy_kwargs=kw))
 
 
 def play_n_games_v3(params, rng_key, input_shape, num_envs, num_simulation, max_depth, max_steps, temp,

@@ -16,6 +16,8 @@ import torch
 from . import dog as DOG
 from . import lib as _L
 from . import muzero_dog as MD
+from .nets import rng_key_to_seed
+from .records import REFERENCE_DTYPES, alloc_records, as_traj, cached, reference_buffers
 
 RULES = dict(enable_teams=True, enable_initial_free_pin=False, enable_circular_board=True, enable_friendly_fire=True,
              enable_start_blocking=True, enable_jump_in_goal_area=False, must_traverse_start=True,
@@ -79,24 +81,8 @@ class DogSelfPlay:
         if seed is not None:
             self.seed = int(seed)
         if self._rec_cache is None or self._rec_cache["act"].shape != (n, T):
-            z = dict(device=dev)
-            self._rec_cache = {
-                "obs": torch.empty((n, T, MD.NUM_CHANNELS, 56), dtype=torch.int8, **z),
-                "act": torch.empty((n, T), dtype=torch.int32, **z),
-                "rew": torch.empty((n, T), dtype=torch.int32, **z),
-                "val": torch.empty((n, T), dtype=torch.float32, **z),
-                "pol": torch.empty((n, T, MD.NUM_ACTIONS), dtype=torch.float32, **z),
-                "mask": torch.empty((n, T), dtype=torch.float32, **z),
-                "player": torch.empty((n, T), dtype=torch.int32, **z),
-                "team": torch.empty((n, T), dtype=torch.int32, **z),
-                "discount": torch.empty((n, T), dtype=torch.int32, **z),
-                "idx": torch.empty((n,), dtype=torch.int32, **z),
-            }
-            t = _L.MuzTraj()
-            for k, v in self._rec_cache.items():
-                setattr(t, k, v.data_ptr())
-            t.max_steps = T
-            self._traj = t
+            self._rec_cache = alloc_records(n, T, MD.NUM_CHANNELS, MD.NUM_ACTIONS, dev)
+            self._traj = as_traj(self._rec_cache, T)
         self.rec = self._rec_cache
         self.rec["idx"].zero_()
         i32 = dict(dtype=torch.int32, device=dev)
@@ -136,9 +122,6 @@ class DogSelfPlay:
         return self.B * int(nturns)
 
 
-REFERENCE_DTYPES = {"obs": torch.float32, "act": torch.int32, "rew": torch.int32, "val": torch.float32,
-                    "pol": torch.float32, "mask": torch.float32, "player": torch.int32, "team": torch.int32,
-                    "discount": torch.int32, "idx": torch.int32}
 _ENGINE = {}
 
 
@@ -150,16 +133,11 @@ def play_n_games_v3(params, rng_key, input_shape, num_envs, num_simulation, max_
     torch.int8`` keeps the engine's exact int8 copy --, act / rew / player / team / discount int32, val / mask fp32,
     pol fp32 [.., 806], idx).  ``params``: the slice's flat parameter dict or a DeviceDogNet; ``rng_key``: int or
     uint32[2] key (the engine's counter streams, not threefry)."""
-    from . import nets as N
     if tuple(int(x) for x in input_shape) != (MD.NUM_CHANNELS, 56):
         raise ValueError(f"input_shape {tuple(input_shape)} != ({MD.NUM_CHANNELS}, 56)")
     net = MD.as_device_net(params)
     key = (id(net), int(num_envs), int(num_simulation), int(max_depth))
-    sp = _ENGINE.get(key)
-    if sp is None or sp.net is not net:
-        _ENGINE.clear()
-        sp = _ENGINE[key] = DogSelfPlay(net, num_envs, num_simulation, max_depth, temp)
-    buf = sp.play_stream(num_envs, max_steps, temperature=temp, seed=N.rng_key_to_seed(rng_key))
-    from .game_agent import reference_buffers
+    sp = cached(_ENGINE, key, net, lambda: DogSelfPlay(net, num_envs, num_simulation, max_depth, temp))
+    buf = sp.play_stream(num_envs, max_steps, temperature=temp, seed=rng_key_to_seed(rng_key))
     return reference_buffers(buf, dict(REFERENCE_DTYPES, obs=obs_dtype))   # copies: the engine reuses its buffers
 

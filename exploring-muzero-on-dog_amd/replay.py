@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
+from .records import as_traj, as_traj_chance
 
 GAMMA = 0.997
 TERMINAL_RATIO = 0.25
@@ -83,11 +84,7 @@ class VectorizedReplayBuffer:
 
     @staticmethod
     def _traj(b: dict) -> _L.MuzTraj:
-        t = _L.MuzTraj()
-        for k in ("obs", "act", "rew", "val", "pol", "mask", "player", "team", "discount", "idx"):
-            setattr(t, k, b[k].data_ptr())
-        t.max_steps = b["act"].shape[1]
-        return t
+        return as_traj(b, b["act"].shape[1])
 
     # dtype of each trajectory field in the device ring / muz_traj (obs: int8 values 0..4)
     TRAJ_DTYPES = {"obs": torch.int8, "act": torch.int32, "rew": torch.int32, "val": torch.float32,
@@ -149,7 +146,6 @@ class VectorizedReplayBuffer:
     def save_packed(self, packed: dict):
         """Games packed by transfer.pack (possibly received from another rank by transfer.gather_packed)
         into the ring, with the same slot rule as save_games_from_buffers."""
-        from .transfer import chance_struct, traj_struct
         n = packed["idx"].shape[0]
         if n == 0:
             return
@@ -159,8 +155,8 @@ class VectorizedReplayBuffer:
         if max_len > self.max_episode_length:
             raise ValueError("a packed game is longer than max_episode_length")
         slots = torch.empty((n,), dtype=torch.int32, device=self.device)
-        ch = chance_struct(packed) if self._chance(packed) is not None else None
-        _L.check(_L.load().muz_ring_save_packed(self.ring(), traj_struct(packed), None if ch is None else ctypes.byref(ch),
+        ch = self._chance(packed)
+        _L.check(_L.load().muz_ring_save_packed(self.ring(), as_traj(packed), None if ch is None else ctypes.byref(ch),
                                                 _L.ptr(packed["row_offset"]), n, max_len, self.position,
                                                 _L.ptr(slots), _L.ptr(self._count), _L.stream_ptr()),
                  "muz_ring_save_packed")
@@ -297,9 +293,7 @@ class VectorizedReplayBufferStochastic(VectorizedReplayBuffer):
     TRAJ_DTYPES = dict(VectorizedReplayBuffer.TRAJ_DTYPES, dice=torch.int32, dice_dist=torch.float32)
 
     def _chance(self, b: dict):
-        ch = _L.MuzTrajChance()
-        ch.dice, ch.dice_dist = b["dice"].data_ptr(), b["dice_dist"].data_ptr()
-        return ch
+        return as_traj_chance(b)
 
     def _extra_outputs(self, B, K, z):
         return {"dice_outcomes": torch.empty((B, K - 1), dtype=torch.int32, **z),

@@ -29,6 +29,7 @@ import torch
 import torch.distributed as dist
 
 from . import lib as _L
+from .records import as_traj, as_traj_chance
 
 CELLS = 56
 
@@ -41,23 +42,6 @@ def fields(obs_channels: int, num_actions: int, chance: bool):
     if chance:
         f += [("dice", torch.int32, ()), ("dice_dist", torch.float32, (6,))]
     return f
-
-
-def traj_struct(rows: dict, max_steps: int = 0) -> _L.MuzTraj:
-    t = _L.MuzTraj()
-    for k in ("obs", "act", "rew", "val", "pol", "mask", "player", "team", "discount", "idx"):
-        setattr(t, k, rows[k].data_ptr() if rows.get(k) is not None and rows[k].numel() else 0)
-    t.max_steps = int(max_steps)
-    return t
-
-
-def chance_struct(rows: dict):
-    if "dice" not in rows:
-        return None
-    c = _L.MuzTrajChance()
-    c.dice = rows["dice"].data_ptr() if rows["dice"].numel() else 0
-    c.dice_dist = rows["dice_dist"].data_ptr() if rows["dice_dist"].numel() else 0
-    return c
 
 
 def pack(buffers: dict) -> dict:
@@ -75,9 +59,8 @@ def pack(buffers: dict) -> dict:
     out = {name: torch.empty((R,) + shp, dtype=dt, device=dev) for name, dt, shp in fields(C, A, chance)}
     out["idx"] = torch.empty((n,), dtype=torch.int32, device=dev)
     out["row_offset"] = off
-    src_ch, dst_ch = chance_struct(buffers), chance_struct(out)
-    _L.check(lib.muz_traj_pack(traj_struct(buffers, T), None if src_ch is None else ctypes.byref(src_ch), _L.ptr(off),
-                               n, C, A, traj_struct(out), None if dst_ch is None else ctypes.byref(dst_ch), s),
+    src_ch, dst_ch = (ctypes.byref(as_traj_chance(b)) if chance else None for b in (buffers, out))
+    _L.check(lib.muz_traj_pack(as_traj(buffers, T), src_ch, _L.ptr(off), n, C, A, as_traj(out), dst_ch, s),
              "muz_traj_pack")
     return out
 

@@ -114,3 +114,23 @@ def test_classic_stream_equals_batch(cuda, games, lanes, T):
     for k in want:
         assert torch.equal(got[k], want[k]), k
     assert eng.last_stats["searches"] == batch.last_stats["searches"]
+
+
+def test_classic_stream_single_lane_equals_batch(cuda):
+    """Three 2-player games through one lane == the batch of three, key by key (dice and dice_dist included): with a
+    single lane every game after the first starts in a lane that the refill reset, and the first in one that the
+    stream's init did, so a mix-up between the init, reset and refill of the lane rows shows here."""
+    from exploring_muzero_on_dog_amd import classic as CL
+    GS, S = _mods()
+    games, T = 3, 12
+    C = CL.num_channels(2)
+    net = S.DeviceClassicNet(CN.init_params(C, seed=12), C)
+    batch = GS.StochasticSelfPlayEngine(net, games, num_players=2, max_steps=T, num_simulations=4, max_depth=3)
+    want = {k: v.clone() for k, v in batch.play(31, 1.0).items()}
+    eng = GS.StochasticSelfPlayEngine(net, 1, num_players=2, max_steps=T, num_simulations=4, max_depth=3)
+    got = eng.play_stream(games, 31, 1.0)
+    assert set(got) == set(want) and {"dice", "dice_dist"} <= set(want)
+    for k in want:
+        assert torch.equal(got[k], want[k]), k
+    assert int(want["idx"].min()) > 0
+    assert eng.last_stats["searches"] == batch.last_stats["searches"]
