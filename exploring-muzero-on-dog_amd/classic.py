@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
+from . import soa as _S
 from .detmadn import set_pins_on_board_host
 
 CELLS = 56
@@ -58,20 +59,7 @@ DEFAULT_RULES = dict(
 
 
 def make_rules(num_players=4, layout=(True, True, True, True), distance=10, starting_player=0, **rules):
-    r = dict(DEFAULT_RULES)
-    unknown = set(rules) - set(r)
-    if unknown:
-        raise TypeError(f"unknown rule(s): {sorted(unknown)}")
-    r.update(rules)
-    c = _L.MuzRules()
-    c.num_players = int(num_players)
-    c.distance = int(distance)
-    for i in range(4):
-        c.layout[i] = int(bool(layout[i]))
-    c.starting_player = int(starting_player)
-    for k, v in r.items():
-        setattr(c, k, int(bool(v)))
-    return c
+    return _S.make_rules(DEFAULT_RULES, num_players, layout, distance, starting_player, **rules)
 
 
 def num_channels(num_players: int) -> int:
@@ -80,7 +68,7 @@ def num_channels(num_players: int) -> int:
 
 
 @dataclass
-class ClassicMADNState:
+class ClassicMADNState(_S.SoAState):
     """SoA batch state. Field c of game b is ``field[c, b]``."""
 
     board: torch.Tensor           # int8 [56, B]
@@ -92,37 +80,10 @@ class ClassicMADNState:
     rules: _L.MuzRules
     num_players: int
 
-    @property
-    def batch(self) -> int:
-        return self.current_player.shape[0]
-
-    def soa(self) -> _L.MuzClassicSoA:
-        s = _L.MuzClassicSoA()
-        s.board = self.board.data_ptr()
-        s.pins = self.pins.data_ptr()
-        s.current_player = self.current_player.data_ptr()
-        s.reward = self.reward.data_ptr()
-        s.done = self.done.data_ptr()
-        s.die = self.die.data_ptr()
-        s.stride = self.batch
-        return s
-
-    def pins_bp(self) -> torch.Tensor:
-        return self.pins.T.reshape(self.batch, self.num_players, 4)
-
-
-def _alloc(batch: int, P: int, rules, device) -> ClassicMADNState:
-    kw = dict(device=device)
-    return ClassicMADNState(
-        board=torch.empty((CELLS, batch), dtype=torch.int8, **kw),
-        pins=torch.empty((P * 4, batch), dtype=torch.int8, **kw),
-        current_player=torch.empty((batch,), dtype=torch.int8, **kw),
-        reward=torch.empty((batch,), dtype=torch.int8, **kw),
-        done=torch.empty((batch,), dtype=torch.uint8, **kw),
-        die=torch.empty((batch,), dtype=torch.int8, **kw),
-        rules=rules,
-        num_players=P,
-    )
+    ROWS = {"board": lambda P: CELLS, "pins": lambda P: P * 4}
+    VECTORS = ("current_player", "reward", "done", "die")
+    DTYPES = {"done": torch.uint8}
+    STRUCT = _L.MuzClassicSoA
 
 
 def _call(name, *args):
@@ -133,7 +94,7 @@ def env_reset(batch: int, num_players=4, layout=(True, True, True, True), distan
               device="cuda", seeds=None, **rules) -> ClassicMADNState:
     """Batched env_reset (classic_madn.py:51-131); ``seeds`` as detmadn.env_reset (a random starting player)."""
     r = make_rules(num_players, layout, distance, starting_player, **rules)
-    st = _alloc(batch, int(num_players), r, device)
+    st = ClassicMADNState.alloc(batch, int(num_players), r, device)
     if seeds is None:
         _call("muz_classic_reset", r, st.soa(), batch, _L.stream_ptr())
     else:
@@ -152,7 +113,7 @@ def state_from_host(pins, current_player, rules: _L.MuzRules, die=None, done=Non
     B, P, _ = pins.shape
     if board is None:
         board = np.stack([set_pins_on_board_host(pins[b]) for b in range(B)])
-    st = _alloc(B, P, rules, device)
+    st = ClassicMADNState.alloc(B, P, rules, device)
     st.board.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(board, np.int8).T)))
     st.pins.copy_(torch.from_numpy(np.ascontiguousarray(pins.reshape(B, P * 4).T)))
     st.current_player.copy_(torch.from_numpy(np.asarray(current_player, np.int8).reshape(B)))

@@ -24,6 +24,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
+from . import soa as _S
 
 CELLS = 56
 ACTIONS = 24
@@ -56,20 +57,7 @@ DEFAULT_RULES = dict(
 
 
 def make_rules(num_players=4, layout=(True, True, True, True), distance=10, starting_player=0, **rules):
-    r = dict(DEFAULT_RULES)
-    unknown = set(rules) - set(r)
-    if unknown:
-        raise TypeError(f"unknown rule(s): {sorted(unknown)}")
-    r.update(rules)
-    c = _L.MuzRules()
-    c.num_players = int(num_players)
-    c.distance = int(distance)
-    for i in range(4):
-        c.layout[i] = int(bool(layout[i]))
-    c.starting_player = int(starting_player)
-    for k, v in r.items():
-        setattr(c, k, int(bool(v)))
-    return c
+    return _S.make_rules(DEFAULT_RULES, num_players, layout, distance, starting_player, **rules)
 
 
 def num_channels(num_players: int) -> int:
@@ -78,7 +66,7 @@ def num_channels(num_players: int) -> int:
 
 
 @dataclass
-class DetMADNState:
+class DetMADNState(_S.SoAState):
     """SoA batch state. Field c of game b is ``field[c, b]``."""
 
     board: torch.Tensor           # int8 [56, B]
@@ -90,45 +78,13 @@ class DetMADNState:
     rules: _L.MuzRules
     num_players: int
 
-    @property
-    def batch(self) -> int:
-        return self.current_player.shape[0]
-
-    def soa(self) -> _L.MuzDetSoA:
-        s = _L.MuzDetSoA()
-        s.board = self.board.data_ptr()
-        s.pins = self.pins.data_ptr()
-        s.current_player = self.current_player.data_ptr()
-        s.reward = self.reward.data_ptr()
-        s.done = self.done.data_ptr()
-        s.action_set = self.action_set.data_ptr()
-        s.stride = self.batch
-        return s
-
-    def pins_bp(self) -> torch.Tensor:
-        """pins as [B, P, 4] (the reference's per-game layout)."""
-        return self.pins.T.reshape(self.batch, self.num_players, 4)
+    ROWS = {"board": lambda P: CELLS, "pins": lambda P: P * 4, "action_set": lambda P: P * 6}
+    VECTORS = ("current_player", "reward", "done")
+    DTYPES = {"done": torch.uint8}
+    STRUCT = _L.MuzDetSoA
 
     def action_set_bp(self) -> torch.Tensor:
         return self.action_set.T.reshape(self.batch, self.num_players, 6)
-
-    def clone(self) -> "DetMADNState":
-        return DetMADNState(self.board.clone(), self.pins.clone(), self.current_player.clone(), self.reward.clone(),
-                            self.done.clone(), self.action_set.clone(), self.rules, self.num_players)
-
-
-def _alloc(batch: int, P: int, rules, device) -> DetMADNState:
-    kw = dict(device=device)
-    return DetMADNState(
-        board=torch.empty((CELLS, batch), dtype=torch.int8, **kw),
-        pins=torch.empty((P * 4, batch), dtype=torch.int8, **kw),
-        current_player=torch.empty((batch,), dtype=torch.int8, **kw),
-        reward=torch.empty((batch,), dtype=torch.int8, **kw),
-        done=torch.empty((batch,), dtype=torch.uint8, **kw),
-        action_set=torch.empty((P * 6, batch), dtype=torch.int8, **kw),
-        rules=rules,
-        num_players=P,
-    )
 
 
 def env_reset(batch: int, num_players=4, layout=(True, True, True, True), distance=10, starting_player=0,
@@ -137,7 +93,7 @@ def env_reset(batch: int, num_players=4, layout=(True, True, True, True), distan
     reference's ``seed`` argument) are needed only by a random starting player (starting_player < 0 or >= P,
     line 62): each game's seat is drawn from its seed (muz_detmadn_reset_seeded)."""
     r = make_rules(num_players, layout, distance, starting_player, **rules)
-    st = _alloc(batch, int(num_players), r, device)
+    st = DetMADNState.alloc(batch, int(num_players), r, device)
     lib = _L.load()
     if seeds is None:
         _L.check(lib.muz_detmadn_reset(r, st.soa(), batch, _L.stream_ptr()), "muz_detmadn_reset")
@@ -172,7 +128,7 @@ def state_from_host(pins, current_player, rules: _L.MuzRules, action_set=None, d
         board = np.stack([set_pins_on_board_host(pins[b]) for b in range(B)])
     if action_set is None:
         action_set = np.full((B, P, 6), 4, dtype=np.int8)
-    st = _alloc(B, P, rules, device)
+    st = DetMADNState.alloc(B, P, rules, device)
     st.board.copy_(torch.from_numpy(np.ascontiguousarray(np.asarray(board, np.int8).T)))
     st.pins.copy_(torch.from_numpy(np.ascontiguousarray(pins.reshape(B, P * 4).T)))
     st.current_player.copy_(torch.from_numpy(np.asarray(current_player, np.int8).reshape(B)))

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import lib as _L
+from . import soa as _S
 
 CELLS = 56
 CARDS = 14
@@ -71,24 +72,11 @@ DISTS_7_4 = all_pin_distributions(7)
 
 
 def make_rules(num_players=4, layout=(True, True, True, True), distance=10, starting_player=0, **rules):
-    r = dict(DEFAULT_RULES)
-    unknown = set(rules) - set(r)
-    if unknown:
-        raise TypeError(f"unknown rule(s): {sorted(unknown)}")
-    r.update(rules)
-    c = _L.MuzRules()
-    c.num_players = int(num_players)
-    c.distance = int(distance)
-    for i in range(4):
-        c.layout[i] = int(bool(layout[i]))
-    c.starting_player = int(starting_player)
-    for k, v in r.items():
-        setattr(c, k, int(bool(v)))
-    return c
+    return _S.make_rules(DEFAULT_RULES, num_players, layout, distance, starting_player, **rules)
 
 
 @dataclass
-class DOGState:
+class DOGState(_S.SoAState):
     """SoA batch state. Field c of game b is ``field[c, b]``."""
 
     board: torch.Tensor           # int8 [56, B]
@@ -107,36 +95,14 @@ class DOGState:
     num_players: int
     seed: int = 0
 
-    @property
-    def batch(self) -> int:
-        return self.current_player.shape[0]
-
-    def soa(self) -> _L.MuzDogSoA:
-        s = _L.MuzDogSoA()
-        for k in ("board", "pins", "deck", "hands", "swap_choices", "current_player", "round_starter", "phase",
-                  "hand_size", "reward", "done", "deal"):
-            setattr(s, k, getattr(self, k).data_ptr())
-        s.stride = self.batch
-        return s
-
-    def pins_bp(self) -> torch.Tensor:
-        return self.pins.T.reshape(self.batch, self.num_players, 4)
+    ROWS = {"board": lambda P: CELLS, "pins": lambda P: P * 4, "deck": lambda P: CARDS, "hands": lambda P: P * CARDS,
+            "swap_choices": lambda P: 4}
+    VECTORS = ("current_player", "round_starter", "phase", "hand_size", "reward", "done", "deal")
+    DTYPES = {"done": torch.uint8, "deal": torch.int32}
+    STRUCT = _L.MuzDogSoA
 
     def hands_bp(self) -> torch.Tensor:
         return self.hands.T.reshape(self.batch, self.num_players, CARDS)
-
-
-def _alloc(batch: int, P: int, rules, device, seed) -> DOGState:
-    kw = dict(device=device)
-    i8 = dict(dtype=torch.int8, **kw)
-    return DOGState(board=torch.empty((CELLS, batch), **i8), pins=torch.empty((P * 4, batch), **i8),
-                    deck=torch.empty((CARDS, batch), **i8), hands=torch.empty((P * CARDS, batch), **i8),
-                    swap_choices=torch.empty((4, batch), **i8), current_player=torch.empty((batch,), **i8),
-                    round_starter=torch.empty((batch,), **i8), phase=torch.empty((batch,), **i8),
-                    hand_size=torch.empty((batch,), **i8), reward=torch.empty((batch,), **i8),
-                    done=torch.empty((batch,), dtype=torch.uint8, **kw),
-                    deal=torch.empty((batch,), dtype=torch.int32, **kw), rules=rules, num_players=P,
-                    seed=int(seed))
 
 
 def _call(name, *args):
@@ -147,7 +113,7 @@ def env_reset(batch: int, num_players=4, layout=(True, True, True, True), distan
               seed=0, device="cuda", **rules) -> DOGState:
     """Batched env_reset (dog.py:83-186): empty board, deck (joker 6, others 8), first deal."""
     r = make_rules(num_players, layout, distance, starting_player, **rules)
-    st = _alloc(batch, int(num_players), r, device, seed)
+    st = DOGState.alloc(batch, int(num_players), r, device, seed=int(seed))
     _call("muz_dog_reset", r, st.soa(), ctypes_u64(seed), batch, _L.stream_ptr())
     return st
 
@@ -162,7 +128,7 @@ def state_from_host(fields: dict, rules: _L.MuzRules, seed=0, device="cuda") -> 
     done / deal."""
     pins = np.asarray(fields["pins"], np.int8)
     B, P, _ = pins.shape
-    st = _alloc(B, P, rules, device, seed)
+    st = DOGState.alloc(B, P, rules, device, seed=int(seed))
 
     def put(dst, a):
         dst.copy_(torch.from_numpy(np.ascontiguousarray(a)))

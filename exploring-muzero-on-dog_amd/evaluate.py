@@ -18,6 +18,10 @@ encode -> root inference -> muz_gumbel_search as one sub-batch, the random seats
 bitmask on the device, and env_step / no_step run on sub-batches of the SoA state.  Differences from the
 reference, on purpose: the starting player cycles over the games (game % P) instead of a jax random draw,
 and the random seats use torch's generator (the reference's jax keys are not restated).
+
+The classic-MADN and the DOG harness (MuZero_Classic_MADN/evaluate_agent_stochastic.py, MuZero_DOG/evaluate_agent.py)
+run the same four-seat loop (_four_seats around _turn); what differs between the three games is in _Det, _Classic and
+_Dog.
 """
 from __future__ import annotations
 
@@ -25,10 +29,14 @@ import math
 
 import torch
 
+from . import classic as CL
 from . import detmadn as E
+from . import dog as DOG
 from . import lib as _L
 from . import mcts as M
+from . import muzero_dog as MD
 from . import nets as N
+from . import stochastic as ST
 
 # evaluate_agent.py:777-864 (the variant evaluate_agent_parallel runs); 509-603 uses 0.5 / 5 / 3 / 1.5 / 2.5
 RULE_AGENT = dict(temperature=0.25, goal_bonus=5.0, out_many=3.0, out_few=2.0, hit_bonus=2.0)
@@ -36,20 +44,22 @@ RULE_AGENT = dict(temperature=0.25, goal_bonus=5.0, out_many=3.0, out_few=2.0, h
 # MuZero_det_MADN/evaluate_agent.py uses the game_agent.py rules
 RULES = dict(E.SELFPLAY_RULES)
 
+# classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
+# defaults: no dice rethrow)
+CLASSIC_RULES = dict(enable_teams=True, enable_initial_free_pin=True, enable_circular_board=False,
+                     enable_friendly_fire=True, enable_start_blocking=False, enable_jump_in_goal_area=True,
+                     enable_start_on_1=True, enable_bonus_turn_on_6=True, must_traverse_start=False,
+                     enable_dice_rethrow=False)
+# do_rule_based of play_eval_loop_jitted (806-866); NUM_SIMULATIONS / MAX_DEPTH / TEMPERATURE of 950-952
+CLASSIC_RULE_AGENT = dict(temperature=0.25, goal_bonus=5.0, out_many=3.0, out_few=2.0, hit_bonus=2.5)
+CLASSIC_SIMULATIONS, CLASSIC_DEPTH = 75, 50
 
-def _sub(env: E.DetMADNState, idx: torch.Tensor) -> E.DetMADNState:
-    return E.DetMADNState(env.board[:, idx].contiguous(), env.pins[:, idx].contiguous(),
-                          env.current_player[idx].contiguous(), env.reward[idx].contiguous(),
-                          env.done[idx].contiguous(), env.action_set[:, idx].contiguous(), env.rules, env.num_players)
-
-
-def _put(env: E.DetMADNState, idx: torch.Tensor, sub: E.DetMADNState):
-    env.board[:, idx] = sub.board
-    env.pins[:, idx] = sub.pins
-    env.current_player[idx] = sub.current_player
-    env.reward[idx] = sub.reward
-    env.done[idx] = sub.done
-    env.action_set[:, idx] = sub.action_set
+# DOG, MuZero_DOG/evaluate_agent.py:530-541; NUM_SIMULATIONS / MAX_DEPTH 544-545, TEMPERATURE 0.20 (552: the value the
+# script runs with)
+DOG_RULES = dict(enable_teams=True, enable_initial_free_pin=False, enable_circular_board=True, enable_friendly_fire=True,
+                 enable_start_blocking=True, enable_jump_in_goal_area=False, must_traverse_start=True,
+                 disable_swapping=False, disable_hot_seven=False, disable_joker=False)
+DOG_SIMULATIONS, DOG_DEPTH, DOG_TEMPERATURE = 100, 50, 0.2
 
 
 def random_legal(bits: torch.Tensor, gen: torch.Generator) -> torch.Tensor:
@@ -93,10 +103,10 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
         idx = torch.arange(sp, num_games, P, device=device)
         if idx.numel():
             sub = E.env_reset(idx.numel(), num_players=P, starting_player=sp, device=device, **r)
-            _put(env, idx, sub)
+            env.put(idx, sub)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
-    ws = M.SearchWorkspace(num_games, num_simulations, device) if net is not None else None
+    ws = _Det.workspace(num_games, num_simulations, device) if net is not None else None
     for turn in range(max_turns):
         active = env.done == 0
         if not bool(active.any()):
@@ -110,23 +120,11 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
         ag = (mover & agent_seat).nonzero().flatten() if net is not None else mover.new_zeros(0, dtype=torch.long)
         rd = (mover & ~agent_seat).nonzero().flatten() if net is not None else mover.nonzero().flatten()
         if ag.numel():
-            sub = _sub(env, ag)
-            obs = E.encode_board(sub)
-            out, _ = M.muzero_mcts(net, obs, bits[ag], num_simulations, max_depth, 0.0, seed=seed, turn=turn,
-                                       workspace=ws, **skw)
-            act[ag] = out.action
+            act[ag] = _Det.search(net, env.take(ag), bits[ag], None, num_simulations, max_depth, 0.0, seed, turn, ws,
+                                  skw)
         if rd.numel():
             act[rd] = random_legal(bits[rd], gen)
-        step = mover.nonzero().flatten()
-        if step.numel():
-            sub = _sub(env, step)
-            E.env_step(sub, act[step])
-            _put(env, step, sub)
-        nos = (active & ~has).nonzero().flatten()
-        if nos.numel():
-            sub = _sub(env, nos)
-            E.no_step(sub)
-            _put(env, nos, sub)
+        _Det.advance(env, act, active, mover)
     w = winners(env, teams)
     in_goal = (env.pins_bp().long() >= 40).sum(dim=2).float().mean(dim=0)
     return {"games": num_games, "wins": int(w[:, 0].sum()), "seat_wins": w.sum(dim=0).tolist(),
@@ -166,32 +164,6 @@ def compare_agents_statistically(net1, net2, num_games: int = 1000, batch_size: 
     return z_test(w1, w2, num_games)
 
 
-# ---- four seats: evaluate_agent_parallel (evaluate_agent.py:253-311, 715-960) ----------------------------
-def _search_kwargs(search: str) -> dict:
-    """muzero_mcts keywords of an evaluation seat's search: today's Gumbel call, or the PUCT muzero_policy without
-    root noise (the classical MuZero evaluation agent at temperature 0)."""
-    if search == "gumbel":
-        return {}
-    if search == "puct":
-        return {"policy": "puct", "dirichlet_fraction": 0.0}
-    raise ValueError(f"unknown search {search!r} ('gumbel' or 'puct')")
-
-
-def policy_action(env: E.DetMADNState, legal: torch.Tensor, mode: str, seed: int, turn: int, agent: dict | None = None,
-                  game_id: torch.Tensor | None = None) -> torch.Tensor:
-    """The random ('random_agent') or rule-based ('rule_based_agent') action of every game (int32 [B], -1
-    without a legal action), one launch over the batch (muz_detmadn_policy_action)."""
-    m = {"random_agent": 0, "rule_based_agent": 1}[mode]
-    a = dict(RULE_AGENT if agent is None else agent)
-    ag = _L.MuzRuleAgent(a["temperature"], a["goal_bonus"], a["out_many"], a["out_few"], a["hit_bonus"])
-    out = torch.empty((env.batch,), dtype=torch.int32, device=env.board.device)
-    gid = None if game_id is None else game_id.to(device=out.device, dtype=torch.int32).contiguous()
-    _L.check(_L.load().muz_detmadn_policy_action(env.rules, env.soa(), _L.ptr(legal.contiguous()), m, ag,
-                                                 int(seed) & ((1 << 64) - 1), int(turn), _L.ptr(gid), _L.ptr(out),
-                                                 env.batch, _L.stream_ptr()), "muz_detmadn_policy_action")
-    return out
-
-
 def _seats(rules, P):
     """Seat (start cell / 10) of each player after env_reset's layout fix-up (deterministic_madn.py:70-74)."""
     lay = [bool(rules.layout[i]) for i in range(4)]
@@ -228,6 +200,258 @@ def calculate_progress(env: E.DetMADNState, must_traverse_start: bool = False) -
     return total.float()
 
 
+# ---- the scripted seats ------------------------------------------------------------------------------------------
+def _search_kwargs(search: str) -> dict:
+    """muzero_mcts keywords of an evaluation seat's search: today's Gumbel call, or the PUCT muzero_policy without
+    root noise (the classical MuZero evaluation agent at temperature 0)."""
+    if search == "gumbel":
+        return {}
+    if search == "puct":
+        return {"policy": "puct", "dirichlet_fraction": 0.0}
+    raise ValueError(f"unknown search {search!r} ('gumbel' or 'puct')")
+
+
+def _policy_action(entry: str, defaults: dict, env, legal, mode, seed, turn, agent, game_id) -> torch.Tensor:
+    m = {"random_agent": 0, "rule_based_agent": 1}[mode]
+    a = dict(defaults if agent is None else agent)
+    ag = _L.MuzRuleAgent(a["temperature"], a["goal_bonus"], a["out_many"], a["out_few"], a["hit_bonus"])
+    out = torch.empty((env.batch,), dtype=torch.int32, device=env.board.device)
+    gid = None if game_id is None else game_id.to(device=out.device, dtype=torch.int32).contiguous()
+    _L.check(getattr(_L.load(), entry)(env.rules, env.soa(), _L.ptr(legal.contiguous()), m, ag,
+                                       int(seed) & ((1 << 64) - 1), int(turn), _L.ptr(gid), _L.ptr(out), env.batch,
+                                       _L.stream_ptr()), entry)
+    return out
+
+
+def policy_action(env: E.DetMADNState, legal: torch.Tensor, mode: str, seed: int, turn: int, agent: dict | None = None,
+                  game_id: torch.Tensor | None = None) -> torch.Tensor:
+    """The random ('random_agent') or rule-based ('rule_based_agent') action of every game (int32 [B], -1
+    without a legal action), one launch over the batch (muz_detmadn_policy_action)."""
+    return _policy_action("muz_detmadn_policy_action", RULE_AGENT, env, legal, mode, seed, turn, agent, game_id)
+
+
+def classic_policy_action(env, legal: torch.Tensor, mode: str, seed: int, turn: int, agent: dict | None = None,
+                          game_id: torch.Tensor | None = None) -> torch.Tensor:
+    """The classic random ('random_agent', do_random 800-804) or rule-based ('rule_based_agent', do_rule_based
+    806-866) pin of every game for the die in the state (int32 [B], -1 without a legal pin), one launch
+    (muz_classic_policy_action)."""
+    return _policy_action("muz_classic_policy_action", CLASSIC_RULE_AGENT, env, legal, mode, seed, turn, agent,
+                          game_id)
+
+
+# ---- what differs between the games ------------------------------------------------------------------------------
+def _stepped(env, idx: torch.Tensor, step):
+    """``step`` (in place on a state) applied to the games ``idx`` of ``env``."""
+    if idx.numel():
+        sub = env.take(idx)
+        step(sub)
+        env.put(idx, sub)
+
+
+class _Game:
+    """What an evaluation turn needs to know about a game: _Det, _Classic and _Dog fill it in (namespaces, never
+    instantiated).  ``env`` is the game's environment module, ``RULES`` its evaluation rules; ``search`` returns the
+    actions of a gathered sub-batch, ``scripted`` those of the whole batch."""
+    REFUSED = {}      # scripted agents the game cannot play -> why
+
+    @classmethod
+    def reset(cls, n, sp, seed, device, r):
+        return cls.env.env_reset(n, num_players=4, starting_player=sp, device=device, **r)
+
+    @staticmethod
+    def pre_turn(env, gen):
+        pass
+
+    @classmethod
+    def legal(cls, env):
+        return cls.env.legal_bits(env)
+
+    @classmethod
+    def advance(cls, env, act, active, mover):
+        """env_step on the games that move, no_step on the unfinished ones without a legal action."""
+        step = mover.nonzero().flatten()
+        _stepped(env, step, lambda sub: cls.env.env_step(sub, act[step]))
+        _stepped(env, (active & ~mover).nonzero().flatten(), cls.env.no_step)
+
+
+class _Det(_Game):
+    env, RULES, C = E, RULES, E.num_channels(4)
+    workspace = staticmethod(M.SearchWorkspace)
+    scripted = staticmethod(policy_action)
+
+    @staticmethod
+    def has(bits):
+        return bits != 0
+
+    @staticmethod
+    def random_net(seed, device):
+        return N.DeviceNet(N.init_muzero_params(seed, _Det.C), _Det.C, device=device)
+
+    @staticmethod
+    def as_net(a, device):
+        return N.as_device_net(a, _Det.C, device=device)
+
+    @staticmethod
+    def search(net, sub, bits, gid, S, D, temperature, seed, turn, ws, skw):
+        out, _ = M.muzero_mcts(net, E.encode_board(sub), bits, S, D, temperature, seed=seed, turn=turn, workspace=ws,
+                               **skw)
+        return out.action
+
+
+class _Classic(_Game):
+    """play_eval_loop_jitted's body_fn (evaluate_agent_stochastic.py:754-900): throw_die (its dice_probabilities,
+    soft lock aware) before the agents move."""
+    env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
+    scripted = staticmethod(classic_policy_action)
+
+    @staticmethod
+    def pre_turn(env, gen):
+        # the uniform draws of the die: torch's generator (the reference's jax key is not restated)
+        CL.throw_die(env, torch.rand((env.batch,), generator=gen, device=env.board.device))
+
+    @staticmethod
+    def has(bits):
+        return (bits & 15) != 0
+
+    @staticmethod
+    def random_net(seed, device):     # a Stochastic MuZero agent with randomly initialised params
+        return ST.DeviceClassicNet(ST.init_classic_params(_Classic.C, seed=seed), _Classic.C, device=device)
+
+    @staticmethod
+    def as_net(a, device):
+        return ST.as_device_classic_net(a, _Classic.C, device=device)
+
+    @staticmethod
+    def workspace(n, S, device):
+        return torch.empty((_L.load().muz_stochastic_workspace_bytes(n, S),), dtype=torch.uint8, device=device)
+
+    @staticmethod
+    def search(net, sub, bits, gid, S, D, temperature, seed, turn, ws, skw):
+        return ST.stochastic_muzero_mcts(net, CL.encode_board(sub), bits, S, D, temperature, seed=seed, turn=turn,
+                                         game_id=gid, workspace=ws)[0]
+
+
+class _Dog(_Game):
+    """Every game steps in its own lane each turn (a lane that does not move, a finished game's included, applies
+    no_step, which leaves a finished game's pins alone), so a game's deals are keyed by its own index."""
+    env, RULES = DOG, DOG_RULES
+    # do_rule_based (evaluate_agent.py:403-480) is det-MADN's agent copied: valid_mask.reshape(4, 6) of the
+    # 806-action DOG mask cannot run, so the reference has no DOG rule-based agent to restate
+    REFUSED = {"rule_based_agent": "MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to "
+                                   "(4, 6) and cannot run; use 'random_agent' or a MuZero agent"}
+    legal = staticmethod(DOG.legal_mask)
+    workspace = staticmethod(MD.SearchWorkspace)
+
+    @staticmethod
+    def reset(n, sp, seed, device, r):   # block sp's deals are keyed by seed + sp
+        return DOG.env_reset(n, num_players=4, starting_player=sp, seed=seed + sp, device=device, **r)
+
+    @staticmethod
+    def has(legal):
+        return (legal != 0).any(dim=1)
+
+    @staticmethod
+    def random_net(seed, device):     # the DOG slice's networks, randomly initialised
+        return MD.DeviceDogNet(MD.init_muzero_params(seed), device=device)
+
+    @staticmethod
+    def as_net(a, device):
+        return MD.as_device_net(a, device=device)
+
+    @staticmethod
+    def scripted(env, legal, mode, seed, turn, agent, gid):
+        return DOG.random_action(legal, seed=seed, turn=turn)
+
+    @staticmethod
+    def search(net, sub, legal, gid, S, D, temperature, seed, turn, ws, skw):
+        lg, v, e = MD.root_inference_fn(net, MD.encode_board(sub), scratch=ws.scratch)
+        pol, _ = MD.gumbel_muzero_policy(net, lg, v, e, legal, S, D, temperature, seed=seed, turn=turn, workspace=ws)
+        return pol.action
+
+    @staticmethod
+    def advance(env, act, active, mover):
+        DOG.env_step(env, act)   # -1: no_step (a game without a legal action, or a finished one)
+
+
+# ---- four seats: evaluate_agent_parallel (evaluate_agent.py:253-311, 715-960) ----------------------------
+def _seat(game, a, i, seed, device):
+    """Seat i of an evaluation: None -> the game's MuZero agent with randomly initialised params, the name of a
+    scripted agent, or anything the game's as_device_*net takes."""
+    if a is None:
+        return game.random_net(1_000_003 * (seed + 1) + i, device)
+    if isinstance(a, str):
+        if a in game.REFUSED:
+            raise ValueError(game.REFUSED[a])
+        if a not in ("rule_based_agent", "random_agent"):
+            raise ValueError(f"unknown agent {a!r}")
+        return a
+    return game.as_net(a, device)
+
+
+def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw) -> bool:
+    """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
+    sub-batch of a seat, or a scripted agent's launch over the batch -- then the game's advance.  False, and nothing
+    played, once every game is finished."""
+    active = env.done == 0
+    game.pre_turn(env, gen)
+    if not bool(active.any()):
+        return False
+    legal = game.legal(env)
+    cp = env.current_player.long()
+    mover = active & game.has(legal)
+    act = torch.full((env.batch,), -1, dtype=torch.int32, device=env.board.device)
+    for s, a in enumerate(seats):
+        sel = mover & (cp == s)
+        if not bool(sel.any()):
+            continue
+        if isinstance(a, str):
+            act = torch.where(sel, game.scripted(env, legal, a, seed, turn, rule_agent, gid), act)
+        else:
+            idx = sel.nonzero().flatten()
+            act[idx] = game.search(a, env.take(idx), legal[idx], gid[idx], S, D, temperature, seed, turn, ws, skw)
+    game.advance(env, act, active, mover)
+    return True
+
+
+def _workspace(game, seats, n, S, device):
+    return game.workspace(n, S, device) if any(not isinstance(x, str) for x in seats) else None
+
+
+def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_turns, rule_agent, device, skw,
+                report_turns=False) -> dict:
+    """4 x batch_size games of ``game``, block i started by player i, played to the end or ``max_turns``; the result
+    tables, with ``report_turns`` also the number of turns the loop ran."""
+    r = dict(game.RULES if rules is None else rules)
+    seats = [_seat(game, a, i, seed, device) for i, a in enumerate(agents)]
+    n = 4 * batch_size
+    env = game.reset(n, 0, seed, device, r)
+    for sp in range(1, 4):
+        env.put(slice(sp * batch_size, (sp + 1) * batch_size), game.reset(batch_size, sp, seed, device, r))
+    gid = torch.arange(n, device=device, dtype=torch.int32)
+    gen = torch.Generator(device=device)
+    gen.manual_seed(seed)
+    ws = _workspace(game, seats, n, S, device)
+    turns = 0
+    for turn in range(max_turns):
+        turns = turn + 1
+        if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw):
+            break
+    return _tables(env, r, batch_size, **({"turns": turns} if report_turns else {}))
+
+
+def _tables(env, r, batch_size, **extra) -> dict:
+    """winners[start][player] and average_progress[start][player] as the reference prints them, plus their totals
+    (wins per player, progress per player = column sum / 4)."""
+    P = env.num_players
+    w = winners(env, bool(r.get("enable_teams", False))) & (env.done != 0)[:, None]
+    prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))
+    win_tab = w.long().reshape(4, batch_size, P).sum(dim=1)
+    prog_tab = prog.reshape(4, batch_size, P).mean(dim=1)
+    return {"games": env.batch, "winners": win_tab.tolist(), "average_progress": prog_tab.tolist(),
+            "wins_per_player": win_tab.sum(dim=0).tolist(), "progress_per_player": (prog_tab.sum(dim=0) / 4).tolist(),
+            "finished": int((env.done != 0).sum()), **extra, "final_state": env}
+
+
 @torch.no_grad()
 def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int = 100, max_depth: int = 50,
                             temperature: float = 0.0, seed: int = 0, rules: dict | None = None, max_turns: int = 2000,
@@ -239,164 +463,11 @@ def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int =
     Gumbel search, or with ``search="puct"`` mcts.muzero_policy without root noise.
     Returns winners[start][player] and average_progress[start][player] as the reference prints them, plus
     their totals (wins per player, progress per player = column sum / 4)."""
-    r = dict(RULES if rules is None else rules)
-    skw = _search_kwargs(search)
-    P = 4
-    C = E.num_channels(P)
-    nets = []
-    for i, a in enumerate(agents):
-        if a is None:
-            nets.append(N.DeviceNet(N.init_muzero_params(1_000_003 * (seed + 1) + i, C), C, device=device))
-        elif isinstance(a, str):
-            if a not in ("rule_based_agent", "random_agent"):
-                raise ValueError(f"unknown agent {a!r}")
-            nets.append(a)
-        else:
-            nets.append(N.as_device_net(a, C, device=device))
-    n = 4 * batch_size
-    env = E.env_reset(n, num_players=P, device=device, **r)
-    for sp in range(1, 4):
-        idx = torch.arange(sp * batch_size, (sp + 1) * batch_size, device=device)
-        _put(env, idx, E.env_reset(batch_size, num_players=P, starting_player=sp, device=device, **r))
-    gid = torch.arange(n, device=device, dtype=torch.int32)
-    ws = M.SearchWorkspace(n, num_simulations, device) if any(not isinstance(x, str) for x in nets) else None
-    for turn in range(max_turns):
-        active = env.done == 0
-        if not bool(active.any()):
-            break
-        bits = E.legal_bits(env)
-        cp = env.current_player.long()
-        has = bits != 0
-        mover = active & has
-        act = torch.full((n,), -1, dtype=torch.int32, device=device)
-        for s, a in enumerate(nets):
-            sel = mover & (cp == s)
-            if not bool(sel.any()):
-                continue
-            if isinstance(a, str):
-                pa = policy_action(env, bits, a, seed, turn, rule_agent, gid)
-                act = torch.where(sel, pa, act)
-            else:
-                idx = sel.nonzero().flatten()
-                sub = _sub(env, idx)
-                out, _ = M.muzero_mcts(a, E.encode_board(sub), bits[idx], num_simulations, max_depth, temperature,
-                                       seed=seed, turn=turn, workspace=ws, **skw)
-                act[idx] = out.action
-        step = mover.nonzero().flatten()
-        if step.numel():
-            sub = _sub(env, step)
-            E.env_step(sub, act[step])
-            _put(env, step, sub)
-        nos = (active & ~has).nonzero().flatten()
-        if nos.numel():
-            sub = _sub(env, nos)
-            E.no_step(sub)
-            _put(env, nos, sub)
-    w = winners(env, bool(r.get("enable_teams", False))) & (env.done != 0)[:, None]
-    prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))
-    win_tab = w.long().reshape(4, batch_size, P).sum(dim=1)
-    prog_tab = prog.reshape(4, batch_size, P).mean(dim=1)
-    return {"games": n, "winners": win_tab.tolist(), "average_progress": prog_tab.tolist(),
-            "wins_per_player": win_tab.sum(dim=0).tolist(), "progress_per_player": (prog_tab.sum(dim=0) / 4).tolist(),
-            "finished": int((env.done != 0).sum()), "final_state": env}
+    return _four_seats(_Det, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns,
+                       rule_agent, device, _search_kwargs(search))
 
 
 # ---- classic MADN: MuZero_Classic_MADN/evaluate_agent_stochastic.py ------------------------------------------------
-# evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's defaults: no dice rethrow)
-CLASSIC_RULES = dict(enable_teams=True, enable_initial_free_pin=True, enable_circular_board=False,
-                     enable_friendly_fire=True, enable_start_blocking=False, enable_jump_in_goal_area=True,
-                     enable_start_on_1=True, enable_bonus_turn_on_6=True, must_traverse_start=False,
-                     enable_dice_rethrow=False)
-# do_rule_based of play_eval_loop_jitted (806-866); NUM_SIMULATIONS / MAX_DEPTH / TEMPERATURE of 950-952
-CLASSIC_RULE_AGENT = dict(temperature=0.25, goal_bonus=5.0, out_many=3.0, out_few=2.0, hit_bonus=2.5)
-CLASSIC_SIMULATIONS, CLASSIC_DEPTH = 75, 50
-
-
-def classic_policy_action(env, legal: torch.Tensor, mode: str, seed: int, turn: int, agent: dict | None = None,
-                          game_id: torch.Tensor | None = None) -> torch.Tensor:
-    """The classic random ('random_agent', do_random 800-804) or rule-based ('rule_based_agent', do_rule_based
-    806-866) pin of every game for the die in the state (int32 [B], -1 without a legal pin), one launch
-    (muz_classic_policy_action)."""
-    m = {"random_agent": 0, "rule_based_agent": 1}[mode]
-    a = dict(CLASSIC_RULE_AGENT if agent is None else agent)
-    ag = _L.MuzRuleAgent(a["temperature"], a["goal_bonus"], a["out_many"], a["out_few"], a["hit_bonus"])
-    out = torch.empty((env.batch,), dtype=torch.int32, device=env.board.device)
-    gid = None if game_id is None else game_id.to(device=out.device, dtype=torch.int32).contiguous()
-    _L.check(_L.load().muz_classic_policy_action(env.rules, env.soa(), _L.ptr(legal.contiguous()), m, ag,
-                                                 int(seed) & ((1 << 64) - 1), int(turn), _L.ptr(gid), _L.ptr(out),
-                                                 env.batch, _L.stream_ptr()), "muz_classic_policy_action")
-    return out
-
-
-def _csub(env, idx: torch.Tensor):
-    from . import classic as CL
-    return CL.ClassicMADNState(env.board[:, idx].contiguous(), env.pins[:, idx].contiguous(),
-                               env.current_player[idx].contiguous(), env.reward[idx].contiguous(),
-                               env.done[idx].contiguous(), env.die[idx].contiguous(), env.rules, env.num_players)
-
-
-def _cput(env, idx: torch.Tensor, sub):
-    env.board[:, idx] = sub.board
-    env.pins[:, idx] = sub.pins
-    env.current_player[idx] = sub.current_player
-    env.reward[idx] = sub.reward
-    env.done[idx] = sub.done
-    env.die[idx] = sub.die
-
-
-def _classic_turn(env, seats, gid, turn, seed, gen, num_simulations, max_depth, temperature, rule_agent, ws,
-                  throw=True):
-    """One turn of every unfinished game (play_eval_loop_jitted's body_fn, 754-900): throw_die (its dice_probabilities,
-    soft lock aware), then per game the agent of its current player -- a stochastic MuZero search ('mcts': a
-    DeviceClassicNet), 'random_agent' or 'rule_based_agent' -- and env_step, or no_step without a legal pin."""
-    from . import classic as CL
-    from . import stochastic as ST
-    n = env.batch
-    active = env.done == 0
-    if throw:
-        # the uniform draws of the die: torch's generator (the reference's jax key is not restated)
-        CL.throw_die(env, torch.rand((n,), generator=gen, device=env.board.device))
-    bits = CL.legal_bits(env)
-    cp = env.current_player.long()
-    has = (bits & 15) != 0
-    mover = active & has
-    act = torch.full((n,), -1, dtype=torch.int32, device=env.board.device)
-    for s, a in enumerate(seats):
-        sel = mover & (cp == s)
-        if not bool(sel.any()):
-            continue
-        if isinstance(a, str):
-            act = torch.where(sel, classic_policy_action(env, bits, a, seed, turn, rule_agent, gid), act)
-        else:
-            idx = sel.nonzero().flatten()
-            sub = _csub(env, idx)
-            out = ST.stochastic_muzero_mcts(a, CL.encode_board(sub), bits[idx], num_simulations, max_depth,
-                                            temperature, seed=seed, turn=turn, game_id=gid[idx], workspace=ws)
-            act[idx] = out[0]
-    step = mover.nonzero().flatten()
-    if step.numel():
-        sub = _csub(env, step)
-        CL.env_step(sub, act[step])
-        _cput(env, step, sub)
-    nos = (active & ~has).nonzero().flatten()
-    if nos.numel():
-        sub = _csub(env, nos)
-        CL.no_step(sub)
-        _cput(env, nos, sub)
-    return bool(active.any())
-
-
-def _classic_seat(a, C, i, seed, device):
-    from . import stochastic as ST
-    if a is None:     # a Stochastic MuZero agent with randomly initialised params
-        return ST.DeviceClassicNet(ST.init_classic_params(C, seed=1_000_003 * (seed + 1) + i), C, device=device)
-    if isinstance(a, str):
-        if a not in ("rule_based_agent", "random_agent"):
-            raise ValueError(f"unknown agent {a!r}")
-        return a
-    return ST.as_device_classic_net(a, C, device=device)
-
-
 @torch.no_grad()
 def evaluate_agent_parallel_classic(agents, batch_size: int = 150, num_simulations: int = CLASSIC_SIMULATIONS,
                                     max_depth: int = CLASSIC_DEPTH, temperature: float = 0.0, seed: int = 0,
@@ -407,35 +478,8 @@ def evaluate_agent_parallel_classic(agents, batch_size: int = 150, num_simulatio
     MuZero, temperature 0, S 75, D 50), None (randomly initialised params), 'rule_based_agent' or 'random_agent';
     4 x batch_size games, block i started by player i; the die thrown every turn; at most 2000 turns.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals."""
-    from . import classic as CL
-    from . import stochastic as ST
-    r = dict(CLASSIC_RULES if rules is None else rules)
-    P = 4
-    C = CL.num_channels(P)
-    seats = [_classic_seat(a, C, i, seed, device) for i, a in enumerate(agents)]
-    n = 4 * batch_size
-    env = CL.env_reset(n, num_players=P, device=device, **r)
-    for sp in range(1, 4):
-        idx = torch.arange(sp * batch_size, (sp + 1) * batch_size, device=device)
-        _cput(env, idx, CL.env_reset(batch_size, num_players=P, starting_player=sp, device=device, **r))
-    gid = torch.arange(n, device=device, dtype=torch.int32)
-    gen = torch.Generator(device=device)
-    gen.manual_seed(seed)
-    ws = None
-    if any(not isinstance(x, str) for x in seats):
-        ws = torch.empty((_L.load().muz_stochastic_workspace_bytes(n, num_simulations),), dtype=torch.uint8,
-                         device=device)
-    for turn in range(max_turns):
-        if not _classic_turn(env, seats, gid, turn, seed, gen, num_simulations, max_depth, temperature, rule_agent,
-                             ws):
-            break
-    w = winners(env, bool(r.get("enable_teams", False))) & (env.done != 0)[:, None]
-    prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))
-    win_tab = w.long().reshape(4, batch_size, P).sum(dim=1)
-    prog_tab = prog.reshape(4, batch_size, P).mean(dim=1)
-    return {"games": n, "winners": win_tab.tolist(), "average_progress": prog_tab.tolist(),
-            "wins_per_player": win_tab.sum(dim=0).tolist(), "progress_per_player": (prog_tab.sum(dim=0) / 4).tolist(),
-            "finished": int((env.done != 0).sum()), "final_state": env}
+    return _four_seats(_Classic, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns,
+                       rule_agent, device, {})
 
 
 @torch.no_grad()
@@ -448,12 +492,10 @@ def play_vs_random_classic(agent, num_games: int, num_simulations: int = CLASSIC
     (env_reset's seed); wins counted at seat 0.  The die is thrown every turn as play_eval_loop_jitted does: the v2
     step as written never throws it, so its games keep env_reset's die 0, have no legal pin and end only at
     MAX_STEPS (oracle/classic_madn.py: valid_action of a fresh state with die 0 is all False)."""
-    from . import classic as CL
     r = dict(CLASSIC_RULES if rules is None else rules)
     P = 4
-    C = CL.num_channels(P)
     teams = bool(r.get("enable_teams", False))
-    ag = _classic_seat(agent, C, 0, seed, device)
+    ag = _seat(_Classic, agent, 0, seed, device)
     seats = [ag, "random_agent", ag if teams else "random_agent", "random_agent"]
     g = torch.Generator().manual_seed(seed)
     seeds = torch.randint(0, 1_000_000, (num_games,), generator=g).tolist()
@@ -462,12 +504,9 @@ def play_vs_random_classic(agent, num_games: int, num_simulations: int = CLASSIC
     gid = torch.arange(num_games, device=device, dtype=torch.int32)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
-    ws = None
-    if not isinstance(ag, str):
-        ws = torch.empty((_L.load().muz_stochastic_workspace_bytes(num_games, num_simulations),), dtype=torch.uint8,
-                         device=device)
+    ws = _workspace(_Classic, seats, num_games, num_simulations, device)
     for turn in range(max_turns):
-        if not _classic_turn(env, seats, gid, turn, seed, gen, num_simulations, max_depth, 0.0, None, ws):
+        if not _turn(_Classic, env, seats, gid, turn, seed, gen, num_simulations, max_depth, 0.0, None, ws, {}):
             break
     w = winners(env, teams) & (env.done != 0)[:, None]
     prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))
@@ -498,29 +537,6 @@ def compare_agents_statistically_classic(agent1, agent2, num_games: int = 1000, 
 
 
 # ---- DOG: MuZero_DOG/evaluate_agent.py --------------------------------------------------------------------------
-# evaluate_agent.py:530-541; NUM_SIMULATIONS / MAX_DEPTH 544-545, TEMPERATURE 0.20 (552: the value the script runs with)
-DOG_RULES = dict(enable_teams=True, enable_initial_free_pin=False, enable_circular_board=True, enable_friendly_fire=True,
-                 enable_start_blocking=True, enable_jump_in_goal_area=False, must_traverse_start=True,
-                 disable_swapping=False, disable_hot_seven=False, disable_joker=False)
-DOG_SIMULATIONS, DOG_DEPTH, DOG_TEMPERATURE = 100, 50, 0.2
-
-
-def _dog_seat(a, i, seed, device):
-    from . import muzero_dog as MD
-    if a is None:     # a MuZero agent with randomly initialised params (the DOG slice's networks)
-        return MD.DeviceDogNet(MD.init_muzero_params(1_000_003 * (seed + 1) + i), device=device)
-    if isinstance(a, str):
-        if a == "rule_based_agent":
-            # do_rule_based (evaluate_agent.py:403-480) is det-MADN's agent copied: valid_mask.reshape(4, 6) of the
-            # 806-action DOG mask cannot run, so the reference has no DOG rule-based agent to restate
-            raise ValueError("MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to (4, 6) "
-                             "and cannot run; use 'random_agent' or a MuZero agent")
-        if a != "random_agent":
-            raise ValueError(f"unknown agent {a!r}")
-        return a
-    return MD.as_device_net(a, device=device)
-
-
 @torch.no_grad()
 def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: int = DOG_SIMULATIONS,
                                 max_depth: int = DOG_DEPTH, temperature: float = DOG_TEMPERATURE, seed: int = 0,
@@ -533,53 +549,5 @@ def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: i
     game's lane applies no_step, which leaves its pins alone), so a game's deals are keyed by its own index.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals.
     Win-rate parity is unpinned: the reference's DOG networks and inference functions are `pass`."""
-    from . import dog as DOG
-    from . import muzero_dog as MD
-    r = dict(DOG_RULES if rules is None else rules)
-    P = 4
-    seats = [_dog_seat(a, i, seed, device) for i, a in enumerate(agents)]
-    n = 4 * batch_size
-    env = DOG.env_reset(n, num_players=P, seed=seed, device=device, **r)
-    for sp in range(1, 4):   # block sp started by player sp (its deals keyed by seed + sp)
-        blk = DOG.env_reset(batch_size, num_players=P, starting_player=sp, seed=seed + sp, device=device, **r)
-        sl = slice(sp * batch_size, (sp + 1) * batch_size)
-        for k in ("board", "pins", "deck", "hands", "swap_choices"):
-            getattr(env, k)[:, sl] = getattr(blk, k)
-        for k in ("current_player", "round_starter", "phase", "hand_size", "reward", "done", "deal"):
-            getattr(env, k)[sl] = getattr(blk, k)
-    ws = MD.SearchWorkspace(n, num_simulations, device) if any(not isinstance(x, str) for x in seats) else None
-    for turn in range(max_turns):
-        active = env.done == 0
-        if not bool(active.any()):
-            break
-        legal = DOG.legal_mask(env)
-        has = (legal != 0).any(dim=1)
-        mover = active & has
-        cp = env.current_player.long()
-        act = torch.full((n,), -1, dtype=torch.int32, device=device)
-        for s, a in enumerate(seats):
-            sel = mover & (cp == s)
-            if not bool(sel.any()):
-                continue
-            if isinstance(a, str):
-                act = torch.where(sel, DOG.random_action(legal, seed=seed, turn=turn), act)
-            else:
-                idx = sel.nonzero().flatten()
-                sub = DOG.DOGState(*(getattr(env, k)[:, idx].contiguous() if getattr(env, k).dim() == 2 else
-                                     getattr(env, k)[idx].contiguous()
-                                     for k in ("board", "pins", "deck", "hands", "swap_choices", "current_player",
-                                               "round_starter", "phase", "hand_size", "reward", "done", "deal")),
-                                   rules=env.rules, num_players=P, seed=env.seed)
-                lg, v, e = MD.root_inference_fn(a, MD.encode_board(sub), scratch=ws.scratch)
-                pol, _ = MD.gumbel_muzero_policy(a, lg, v, e, legal[idx], num_simulations, max_depth, temperature,
-                                                 seed=seed, turn=turn, workspace=ws)
-                act[idx] = pol.action
-        act = torch.where(active, act, torch.full_like(act, -1))
-        DOG.env_step(env, act)   # negative: no_step (a game without a legal action, or a finished one)
-    w = winners(env, bool(r.get("enable_teams", False))) & (env.done != 0)[:, None]
-    prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))
-    win_tab = w.long().reshape(4, batch_size, P).sum(dim=1)
-    prog_tab = prog.reshape(4, batch_size, P).mean(dim=1)
-    return {"games": n, "winners": win_tab.tolist(), "average_progress": prog_tab.tolist(),
-            "wins_per_player": win_tab.sum(dim=0).tolist(), "progress_per_player": (prog_tab.sum(dim=0) / 4).tolist(),
-            "finished": int((env.done != 0).sum()), "turns": turn + 1, "final_state": env}
+    return _four_seats(_Dog, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns, None,
+                       device, {}, report_turns=True)

@@ -54,7 +54,7 @@ class SelfPlayEngine(NativeSelfPlay):
             raise ValueError(f"network expects {net.C} observation channels, {self.P} players give {self.C}")
         r = dict(RULES if rules is None else rules)
         self.rules = E.make_rules(self.P, starting_player=starting_player, **r)
-        self.state = E._alloc(self.n, self.P, self.rules, device)
+        self.state = E.DetMADNState.alloc(self.n, self.P, self.rules, device)
         self._alloc(net.A, _L.load().muz_selfplay_workspace_bytes(self.n, self.C, M.make_cfg(self.S, self.D)), device)
 
     def _search(self, seed, temperature):

@@ -30,7 +30,7 @@ class StochasticSelfPlayEngine(NativeSelfPlay):
         if net.C != self.C:
             raise ValueError(f"network expects {net.C} observation channels, {self.P} players give {self.C}")
         self.rules = E.make_rules(self.P, starting_player=starting_player, **dict(RULES if rules is None else rules))
-        self.state = E._alloc(self.n, self.P, self.rules, device)
+        self.state = E.ClassicMADNState.alloc(self.n, self.P, self.rules, device)
         nbytes = _L.load().muz_classic_selfplay_workspace_bytes(self.n, self.C, ST.make_cfg(self.S, self.D))
         self._alloc(ST.A_CLASSIC, nbytes, device, chance=ST.CHANCE)
 

@@ -38,18 +38,18 @@ def child():
         live = env.done == 0
         mv = (live & (bits != 0)).nonzero().flatten()
         if mv.numel():
-            sub = EV._sub(env, mv)
+            sub = env.take(mv)
             E.env_step(sub, EV.random_legal(bits[mv], gen))
-            EV._put(env, mv, sub)
+            env.put(mv, sub)
         ns = (live & (bits == 0)).nonzero().flatten()
         if ns.numel():
-            sub = EV._sub(env, ns)
+            sub = env.take(ns)
             E.no_step(sub)
-            EV._put(env, ns, sub)
+            env.put(ns, sub)
     bits = E.legal_bits(env)
     ok = ((env.done == 0) & (bits != 0)).nonzero().flatten()
     pick = ok[torch.arange(B, device=dev) % ok.numel()]
-    obs = E.encode_board(EV._sub(env, pick))
+    obs = E.encode_board(env.take(pick))
     bits = bits[pick].contiguous()
     ws = M.SearchWorkspace(B, S, dev)
     lg, v, e = N.root_inference_fn(net, obs, ws.scratch)
