@@ -18,35 +18,6 @@ namespace muz {
 
 namespace {
 
-// ---- the tree arithmetic, bit for bit like the NumPy restatement (tests/_mctx_muzero.py) ---------------------------
-// As in search.hip: no fma contraction, sums over the 24 actions in row_sum24's order, exp and log correctly rounded
-// (exp_cr, log_cr), fp32 sqrt and division as IEEE operations.
-
-// muzero_action_selection's value score of child k: qtransform_by_min_max (the reference's commented call) or
-// qtransform_by_parent_and_siblings (mctx's default, eps 1e-8; nv: the node's value)
-template <int QT>
-__device__ __forceinline__ float value_score(const Kid& k, float nv, const PuctArgs& pa) {
-#pragma clang fp contract(off)
-  const float q = k.reward + k.disc * k.value;
-  const bool vis = k.ok && k.visits > 0;
-  if constexpr (QT == MUZ_QT_MIN_MAX) {
-    return ((vis ? q : pa.min_value) - pa.min_value) / (pa.max_value - pa.min_value);
-  } else {
-    const float safe = vis ? q : nv;
-    const float lo = fminf(nv, row_min(k.ok ? safe : INFINITY));
-    const float hi = fmaxf(nv, row_max(k.ok ? safe : -INFINITY));
-    return ((vis ? q : lo) - lo) / fmaxf(hi - lo, 1e-8f);
-  }
-}
-
-// softmax over the row's A actions (lanes a >= A: 0)
-__device__ __forceinline__ float row_softmax24(float x, bool ok) {
-#pragma clang fp contract(off)
-  const float m = row_max(ok ? x : -INFINITY);
-  const float e = ok ? exp_cr(x - m) : 0.f;
-  return e / row_sum24(e);
-}
-
 template <int QT>
 __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     muz_net_w Wt, PuctArgs pa, const float* __restrict__ root_logits, const float* __restrict__ root_value,

@@ -2,6 +2,8 @@
 // path in LDS, children arrays and node embeddings in the workspace.  k_gumbel_search and k_puct_search are built from
 // one simulation body -- SearchLds (the per-row LDS state), NarrowTree::kid (a node's children), walk (the selection
 // loop around the kernel's score), commit_expansion and commit_backup -- and differ in their root, score and tail.
+// k_env_mcts (env_mcts.hip) is k_puct_search's body and score (value_score, row_softmax24 below) around an expansion
+// that steps the environment instead of the networks, on a carve of its own.
 // k_stochastic_search shares the tree layout and row_argmax and keeps its own walk, expansion and one-lane backup
 // written out (on the shared body it was 0.3 % slower per classic self-play step, and needed 247 VGPRs with
 // commit_backup: profiles/search_body_refactor.log); k_dog_search (806 children per node, its own walk and backup)
@@ -84,6 +86,35 @@ struct Kid {
   int visits, index;
   bool ok;
 };
+
+// ---- the tree arithmetic, bit for bit like the NumPy restatement (tests/_mctx_muzero.py) ---------------------------
+// As in search.hip: no fma contraction, sums over the 24 actions in row_sum24's order, exp and log correctly rounded
+// (exp_cr, log_cr), fp32 sqrt and division as IEEE operations.
+
+// muzero_action_selection's value score of child k: qtransform_by_min_max (the reference's commented call) or
+// qtransform_by_parent_and_siblings (mctx's default, eps 1e-8; nv: the node's value)
+template <int QT>
+__device__ __forceinline__ float value_score(const Kid& k, float nv, const PuctArgs& pa) {
+#pragma clang fp contract(off)
+  const float q = k.reward + k.disc * k.value;
+  const bool vis = k.ok && k.visits > 0;
+  if constexpr (QT == MUZ_QT_MIN_MAX) {
+    return ((vis ? q : pa.min_value) - pa.min_value) / (pa.max_value - pa.min_value);
+  } else {
+    const float safe = vis ? q : nv;
+    const float lo = fminf(nv, row_min(k.ok ? safe : INFINITY));
+    const float hi = fmaxf(nv, row_max(k.ok ? safe : -INFINITY));
+    return ((vis ? q : lo) - lo) / fmaxf(hi - lo, 1e-8f);
+  }
+}
+
+// softmax over the row's A actions (lanes a >= A: 0)
+__device__ __forceinline__ float row_softmax24(float x, bool ok) {
+#pragma clang fp contract(off)
+  const float m = row_max(ok ? x : -INFINITY);
+  const float e = ok ? exp_cr(x - m) : 0.f;
+  return e / row_sum24(e);
+}
 
 // seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.
 __host__ __device__ __forceinline__ int considered_visit(int m, int S, int idx) {

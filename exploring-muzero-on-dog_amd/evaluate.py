@@ -10,6 +10,10 @@
                                 seats, each a MuZero agent (a DeviceNet, or None = randomly initialised
                                 params), 'rule_based_agent' or 'random_agent'; batch_size games per starting
                                 player; winners and calculate_progress (129-195) per starting player.
+  'mcts_agent'                  a seat name beside the scripted ones (det-MADN only): the reference's network-free
+                                MCTS agent (MADN/deterministic_madn.py:481-589: muzero_policy over the real
+                                environment with random-rollout leaf values), mcts.env_muzero_policy on the seat's
+                                gathered sub-batch with the evaluation's S / D, temperature 0 and no root noise.
   policy_action                 the random agent (770-775) and the rule-based agent (777-864) as one device
                                 kernel (muz_detmadn_policy_action), sampling by Gumbel-max on the counter RNG.
 
@@ -43,6 +47,12 @@ RULE_AGENT = dict(temperature=0.25, goal_bonus=5.0, out_many=3.0, out_few=2.0, h
 
 # MuZero_det_MADN/evaluate_agent.py uses the game_agent.py rules
 RULES = dict(E.SELFPLAY_RULES)
+
+# the network-free MCTS seat (mcts.env_muzero_policy); rollout cap of MADN/deterministic_madn.py's rollout
+MCTS_AGENT = "mcts_agent"
+MCTS_ROLLOUT_STEPS = 300
+_NO_ENV_MODEL = ("no environment-model search kernel exists for this game (mcts.env_muzero_policy is det-MADN's); use "
+                 "'random_agent', 'rule_based_agent' where the game has one, or a MuZero agent")
 
 # classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
 # defaults: no dice rethrow)
@@ -89,11 +99,17 @@ def winners(env: E.DetMADNState, teams: bool) -> torch.Tensor:
 @torch.no_grad()
 def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4, num_simulations: int = 50,
                    max_depth: int = 25, seed: int = 42, max_turns: int = 2000, rules: dict | None = None,
-                   device="cuda", *, search: str = "gumbel") -> dict:
+                   device="cuda", *, search: str = "gumbel", rollout_steps: int = MCTS_ROLLOUT_STEPS) -> dict:
     """One batch of games, agent at seat 0 (+2 with teams), random elsewhere.  ``net=None`` makes the
     agent random too (the baseline).  ``search="puct"``: the agent searches with mcts.muzero_policy at temperature 0
-    without root noise.  Returns wins at seat 0, per-seat wins and pins in goal."""
+    without root noise.  ``net="mcts_agent"``: the network-free MCTS agent (mcts.env_muzero_policy with rollouts of
+    at most ``rollout_steps`` turns, keyed by the game's index).  Returns wins at seat 0, per-seat wins and pins in
+    goal."""
     skw = _search_kwargs(search)
+    if isinstance(net, str):
+        net = _seat(_Det, net, 0, seed, device)
+        if net != MCTS_AGENT:
+            raise ValueError(f"play_vs_random: the agent is a network, None or {MCTS_AGENT!r}, not {net!r}")
     r = dict(RULES if rules is None else rules)
     teams = bool(r.get("enable_teams", False)) and num_players == 4
     P = num_players
@@ -106,7 +122,8 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
             env.put(idx, sub)
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
-    ws = _Det.workspace(num_games, num_simulations, device) if net is not None else None
+    ws = _workspace(_Det, [net], num_games, num_simulations, device) if net is not None else None
+    mws = _mcts_workspace(_Det, [net], num_games, num_simulations, device)
     for turn in range(max_turns):
         active = env.done == 0
         if not bool(active.any()):
@@ -119,7 +136,10 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
         mover = active & has
         ag = (mover & agent_seat).nonzero().flatten() if net is not None else mover.new_zeros(0, dtype=torch.long)
         rd = (mover & ~agent_seat).nonzero().flatten() if net is not None else mover.nonzero().flatten()
-        if ag.numel():
+        if ag.numel() and net == MCTS_AGENT:
+            act[ag] = _Det.env_search(env.take(ag), ag, num_simulations, max_depth, 0.0, seed, turn, mws,
+                                      rollout_steps)
+        elif ag.numel():
             act[ag] = _Det.search(net, env.take(ag), bits[ag], None, num_simulations, max_depth, 0.0, seed, turn, ws,
                                   skw)
         if rd.numel():
@@ -252,7 +272,7 @@ class _Game:
     """What an evaluation turn needs to know about a game: _Det, _Classic and _Dog fill it in (namespaces, never
     instantiated).  ``env`` is the game's environment module, ``RULES`` its evaluation rules; ``search`` returns the
     actions of a gathered sub-batch, ``scripted`` those of the whole batch."""
-    REFUSED = {}      # scripted agents the game cannot play -> why
+    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL}      # named agents the game cannot play -> why
 
     @classmethod
     def reset(cls, n, sp, seed, device, r):
@@ -276,6 +296,7 @@ class _Game:
 
 class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
+    REFUSED = {}
     workspace = staticmethod(M.SearchWorkspace)
     scripted = staticmethod(policy_action)
 
@@ -295,6 +316,13 @@ class _Det(_Game):
     def search(net, sub, bits, gid, S, D, temperature, seed, turn, ws, skw):
         out, _ = M.muzero_mcts(net, E.encode_board(sub), bits, S, D, temperature, seed=seed, turn=turn, workspace=ws,
                                **skw)
+        return out.action
+
+    @staticmethod
+    def env_search(sub, gid, S, D, temperature, seed, turn, mws, rollout_steps=MCTS_ROLLOUT_STEPS):
+        """The 'mcts_agent' seat: muzero_policy over the real environment, no root noise, keyed by the games' ids."""
+        out, _ = M.env_muzero_policy(sub, S, D, temperature, rollout_steps=rollout_steps, seed=seed, turn=turn,
+                                     game_id=gid, workspace=mws)
         return out.action
 
 
@@ -338,7 +366,8 @@ class _Dog(_Game):
     # do_rule_based (evaluate_agent.py:403-480) is det-MADN's agent copied: valid_mask.reshape(4, 6) of the
     # 806-action DOG mask cannot run, so the reference has no DOG rule-based agent to restate
     REFUSED = {"rule_based_agent": "MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to "
-                                   "(4, 6) and cannot run; use 'random_agent' or a MuZero agent"}
+                                   "(4, 6) and cannot run; use 'random_agent' or a MuZero agent",
+               MCTS_AGENT: _NO_ENV_MODEL}
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
 
@@ -382,16 +411,16 @@ def _seat(game, a, i, seed, device):
     if isinstance(a, str):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
-        if a not in ("rule_based_agent", "random_agent"):
+        if a not in ("rule_based_agent", "random_agent", MCTS_AGENT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
 
 
-def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw) -> bool:
+def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None) -> bool:
     """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
-    sub-batch of a seat, or a scripted agent's launch over the batch -- then the game's advance.  False, and nothing
-    played, once every game is finished."""
+    sub-batch of a seat (a network's, or the 'mcts_agent' seat's over the environment), or a scripted agent's launch
+    over the batch -- then the game's advance.  False, and nothing played, once every game is finished."""
     active = env.done == 0
     game.pre_turn(env, gen)
     if not bool(active.any()):
@@ -404,7 +433,10 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
         sel = mover & (cp == s)
         if not bool(sel.any()):
             continue
-        if isinstance(a, str):
+        if a == MCTS_AGENT:
+            idx = sel.nonzero().flatten()
+            act[idx] = game.env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws)
+        elif isinstance(a, str):
             act = torch.where(sel, game.scripted(env, legal, a, seed, turn, rule_agent, gid), act)
         else:
             idx = sel.nonzero().flatten()
@@ -415,6 +447,10 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
 
 def _workspace(game, seats, n, S, device):
     return game.workspace(n, S, device) if any(not isinstance(x, str) for x in seats) else None
+
+
+def _mcts_workspace(game, seats, n, S, device):
+    return M.EnvSearchWorkspace(n, S, device) if any(isinstance(x, str) and x == MCTS_AGENT for x in seats) else None
 
 
 def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_turns, rule_agent, device, skw,
@@ -431,10 +467,11 @@ def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_tu
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     ws = _workspace(game, seats, n, S, device)
+    mws = _mcts_workspace(game, seats, n, S, device)
     turns = 0
     for turn in range(max_turns):
         turns = turn + 1
-        if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw):
+        if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws):
             break
     return _tables(env, r, batch_size, **({"turns": turns} if report_turns else {}))
 
@@ -457,9 +494,10 @@ def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int =
                             temperature: float = 0.0, seed: int = 0, rules: dict | None = None, max_turns: int = 2000,
                             rule_agent: dict | None = None, device="cuda", *, search: str = "gumbel") -> dict:
     """evaluate_agent_parallel (evaluate_agent.py:253-311): `agents` = the four seats (player indices 0-3),
-    each a DeviceNet, None (a MuZero agent with randomly initialised params), 'rule_based_agent' or
-    'random_agent'.  4 x batch_size games, block i started by player i (jnp.repeat(arange(4), batch_size)),
-    at most 2000 turns; MuZero seats search with S / D / temperature (evaluate_agent.py:938-940 defaults) -- the
+    each a DeviceNet, None (a MuZero agent with randomly initialised params), 'rule_based_agent',
+    'random_agent' or 'mcts_agent' (the network-free MCTS over the environment, mcts.env_muzero_policy with S / D,
+    temperature and no root noise).  4 x batch_size games, block i started by player i
+    (jnp.repeat(arange(4), batch_size)), at most 2000 turns; MuZero seats search with S / D / temperature (evaluate_agent.py:938-940 defaults) -- the
     Gumbel search, or with ``search="puct"`` mcts.muzero_policy without root noise.
     Returns winners[start][player] and average_progress[start][player] as the reference prints them, plus
     their totals (wins per player, progress per player = column sum / 4)."""

@@ -234,6 +234,10 @@ class MuzPuctCfg(ctypes.Structure):
                 ("turn", ctypes.c_int32), ("seed", ctypes.c_uint64)]
 
 
+class MuzEnvMctsCfg(ctypes.Structure):
+    _fields_ = [("rollout_steps", ctypes.c_int32)]
+
+
 class MuzSearchCfg(ctypes.Structure):
     _fields_ = [("num_simulations", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("max_num_considered", ctypes.c_int32), ("value_scale", ctypes.c_float),
@@ -371,6 +375,10 @@ SIGNATURES = {
     "muz_considered_visits": (ctypes.c_int, [ctypes.c_int32, ctypes.c_int32, vp]),
     "muz_puct_search": (ctypes.c_int, [ctypes.POINTER(MuzNetW), ctypes.POINTER(MuzPuctCfg), vp, vp, vp, vp, vp,
                                        vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp, vp, vp, vp]),
+    "muz_detmadn_mcts_tree_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(MuzPuctCfg)]),
+    "muz_detmadn_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzPuctCfg),
+                                        ctypes.POINTER(MuzEnvMctsCfg), MuzDetSoA, vp, vp, vp, ctypes.c_int32, vp,
+                                        ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
     "muz_selfplay_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),
     "muz_detmadn_selfplay": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzNetW),
                                             ctypes.POINTER(MuzSearchCfg), MuzDetSoA, MuzTraj, ctypes.c_int32, vp,

@@ -4,7 +4,9 @@ The whole ``mctx.gumbel_muzero_policy`` call (S simulations of select / expand /
 persistent HIP kernel (csrc/search.hip); the root inference runs first (csrc/nets.hip).  The reference's
 second policy, the ``mctx.muzero_policy`` call it keeps commented (685-697: PUCT, Dirichlet root noise,
 visit-count weights), is ``muzero_policy`` here: another persistent kernel (csrc/puct_search.hip) on the same
-workspace, chosen with ``policy="puct"``.
+workspace, chosen with ``policy="puct"``.  ``env_muzero_policy`` is the reference's network-free agent
+(MADN/deterministic_madn.py:481-589): the same ``muzero_policy`` with the det-MADN environment as its model and random
+rollouts as leaf values (csrc/env_mcts.hip), on a workspace of its own.
 """
 from __future__ import annotations
 
@@ -133,6 +135,66 @@ def muzero_policy(net: _N.DeviceNet, root_logits, root_value, root_embedding, le
                                  _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action), _L.ptr(weights),
                                  _L.ptr(value), _L.stream_ptr()), "muz_puct_search")
     return PolicyOutput(action, weights), value
+
+
+class EnvSearchWorkspace:
+    """Device workspace of env_muzero_policy for B searches: the tree's own carve (muz_detmadn_mcts_tree_bytes:
+    children arrays and a 64-byte state row per node, no latent slots)."""
+
+    def __init__(self, batch: int, num_simulations: int, device="cuda"):
+        cfg = make_puct_cfg(num_simulations, 1)
+        self.batch, self.S = batch, num_simulations
+        nbytes = _L.load().muz_detmadn_mcts_tree_bytes(batch, cfg)
+        if nbytes < 0:
+            raise _L.MuzError(f"env_muzero_policy: num_simulations {num_simulations} is outside the kernel's limits")
+        self.tree = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+    def fits(self, batch, S):
+        return batch <= self.batch and S <= self.S
+
+    def rollout_turns(self, batch: int) -> torch.Tensor:
+        """int32 [batch]: the rollout turns each game of the last search of ``batch`` games played."""
+        return self.tree[:4 * batch].view(torch.int32)
+
+
+def env_muzero_policy(env, num_simulations, max_depth, temperature=0.0, *, rollout_steps=300, seed, turn,
+                      game_id=None, workspace: EnvSearchWorkspace | None = None, summary=False, qtransform="min_max",
+                      min_value=-1.0, max_value=1.0, dirichlet_fraction=0.0, dirichlet_alpha=0.3, pb_c_init=1.25,
+                      pb_c_base=19652.0, dirichlet=None, gumbel=None):
+    """The network-free MCTS agent of the reference (MADN/deterministic_madn.py:481-589 with
+    MADN/simulate_deterministicMADN.py:12-35): mctx.muzero_policy whose model is the det-MADN environment itself --
+    prior logits 100 legal + 200 winning, random-rollout leaf values of at most ``rollout_steps`` turns -- on the
+    states of ``env`` (a detmadn.DetMADNState, read only), one persistent kernel (csrc/env_mcts.hip).  The semantics
+    the reference leaves open are fixed in include/muz.h (muz_detmadn_mcts); parity with the reference is unpinned.
+    The keywords after ``summary`` are muzero_policy's, with no root noise by default (an evaluation agent).  A game
+    that is finished or has no legal action is not searched: action -1, weights 0, value 0.
+    Returns (PolicyOutput, root_value), with ``summary`` also search_tree.summary()'s visit_counts (int32 [B, 24]) and
+    qvalues (fp32 [B, 24]; unvisited children 0)."""
+    from . import detmadn as _E
+    if not isinstance(env, _E.DetMADNState):
+        raise TypeError("env_muzero_policy searches det-MADN states (detmadn.DetMADNState): no environment-model "
+                        f"kernel exists for {type(env).__name__}")
+    lib = _L.load()
+    B = env.batch
+    dev = env.board.device
+    cfg = make_puct_cfg(num_simulations, max_depth, temperature, qtransform, min_value, max_value, dirichlet_fraction,
+                        dirichlet_alpha, pb_c_init, pb_c_base, seed, turn)
+    mcfg = _L.MuzEnvMctsCfg(int(rollout_steps))
+    if workspace is None or not workspace.fits(B, num_simulations):
+        workspace = EnvSearchWorkspace(B, num_simulations, dev)
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, _E.ACTIONS), dtype=torch.float32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    visits = torch.empty((B, _E.ACTIONS), dtype=torch.int32, device=dev) if summary else None
+    qvalues = torch.empty((B, _E.ACTIONS), dtype=torch.float32, device=dev) if summary else None
+    dn = None if dirichlet is None else dirichlet.to(device=dev, dtype=torch.float32).contiguous()
+    g = None if gumbel is None else gumbel.to(device=dev, dtype=torch.float32).contiguous()
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).contiguous()
+    _L.check(lib.muz_detmadn_mcts(env.rules, cfg, mcfg, env.soa(), _L.ptr(dn), _L.ptr(g), _L.ptr(gid), B,
+                                  _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action), _L.ptr(weights),
+                                  _L.ptr(value), _L.ptr(visits), _L.ptr(qvalues), _L.stream_ptr()), "muz_detmadn_mcts")
+    out = (PolicyOutput(action, weights), value)
+    return out + (visits, qvalues) if summary else out
 
 
 def muzero_mcts(net: _N.DeviceNet, observations, legal_bits, num_simulations, max_depth, temperature,

@@ -458,6 +458,44 @@ int muz_puct_search(const muz_net_w* w /*host*/, const muz_puct_cfg* cfg /*host*
                     int64_t workspace_bytes, int32_t* action, float* action_weights, float* root_value_out,
                     void* stream);
 
+/* ---- network-free MCTS agent for det-MADN: muzero_policy over the real environment -----------------------
+ * The reference's MCTS whose model is the environment itself, with random-rollout leaf values
+ * (MADN/deterministic_madn.py:481-589 winning_action / policy_function / rollout / value_function / root_fn /
+ * recurrent_fn, driven by MADN/simulate_deterministicMADN.py:12-35; TicTacToe/mcts.py:9-23 is the same construction).
+ * That path cannot run as written (rollout returns a shape-(4,) array, the driver lacks its imports) and discounts by
+ * -1 even when the same side moves again, so parity with it is UNPINNED; the definition is tests/_env_mcts.py, which
+ * the kernel (csrc/env_mcts.hip) equals bit for bit.  For a state s, side(p) = p % 2 with teams, else p:
+ *   legal(s)    the 24-bit valid_action mask; wins(s): bit a set iff a is legal and env_step(s, a) returns reward 1
+ *   prior       logits 100 legal + 200 wins; actions outside the node's mask are masked at every node (a node that is
+ *               finished, or has no legal action after the passes, counts as all 24 actions legal)
+ *   transition  env_step, then no_step while the state is not done and has no legal action (at most 4 times);
+ *               reward env_step's; discount 0 if done, +1 if the side to move is the side that moved, else -1
+ *   value       0 if done; else a rollout of at most rollout_steps turns (no_step without a legal action, else a uniform
+ *               pick among wins if any, else among legal: the k-th set bit, k = min(floor(u count), count - 1), u from
+ *               the counter RNG of (seed, game, turn, node -- 0 the root, i + 1 simulation i --, rollout turn)):
+ *               +1 if the side to move at the rollout's start has won, -1 if another side has, 0 at the cap
+ *   search      muz_puct_search's, muz_puct_cfg whole (Dirichlet fraction 0 for evaluation)
+ * A root state that is done or has no legal action is not searched: action -1, weights 0, value 0. */
+typedef struct muz_env_mcts_cfg {
+  int32_t rollout_steps;   /* 300 (the reference's cap); 0 = every leaf value is 0; at most 1000 */
+} muz_env_mcts_cfg;
+/* Bytes of the tree's own workspace: per game an int32 count of rollout turns, then per node six 32-wide children
+ * arrays and a 64-byte state row.  -1 for a null cfg, n < 0 or S / D outside the limits.  (Not a *_workspace_bytes
+ * name: those are the network searches' and self-play drivers' carves, a closed set whose sizes tests/test_capi.py
+ * pins; this carve is pinned in tests/test_env_mcts_host.py.) */
+int64_t muz_detmadn_mcts_tree_bytes(int32_t n, const muz_puct_cfg* cfg /*host*/);
+/* state is read only.  dirichlet / gumbel / game_id as muz_puct_search.  Outputs: action [n], action_weights [n][24],
+ * root_value [n], and search_tree.summary()'s visit_counts [n][24] / qvalues [n][24] (each nullable; unvisited
+ * children report 0).  After the call the first n int32 of the workspace hold each game's number of rollout turns.
+ * MUZ_E_UNSUPPORTED: what muz_puct_search refuses of cfg, rollout_steps outside 0..1000, rules the det-MADN entry
+ * points refuse.  MUZ_E_INVALID: a null pointer, a workspace shorter than muz_detmadn_mcts_tree_bytes or not
+ * 16-byte aligned.  Checked before any launch; n == 0 returns MUZ_OK; stream-ordered, no global state. */
+int muz_detmadn_mcts(const muz_rules* rules /*host*/, const muz_puct_cfg* cfg /*host*/,
+                     const muz_env_mcts_cfg* mcfg /*host*/, muz_detmadn_soa state, const float* dirichlet,
+                     const float* gumbel, const int32_t* game_id, int32_t n, void* workspace, int64_t workspace_bytes,
+                     int32_t* action, float* action_weights, float* root_value, int32_t* visit_counts,
+                     float* qvalues, void* stream);
+
 /* ---- self-play (MuZero_det_MADN/game_agent.py:50-192) ----------------------------------------------
  * Trajectory buffers [n][T] per game, T = max_steps, mirroring play_batch_of_games_jitted's dict
  * (game_agent.py:158-169); obs is stored int8 (values 0..4, the reference keeps them as fp32). */
