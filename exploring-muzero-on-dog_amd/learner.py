@@ -1247,6 +1247,13 @@ def _chain_backward(chain, G, H, grad_scale, apps, P, B, Nn, G0=None):
 class MuZeroNets:
     """Flax-named fp32 parameters of (RepresentationNetwork2, DynamicsNetwork4, PredictionNetwork4)."""
 
+    SHAPE_ARGS = 2      # how many of (C, A) the constructor takes after ``params`` (a game fixes the rest)
+
+    @classmethod
+    def from_params(cls, flat: dict, device="cuda", dtype=torch.float32):
+        """A flat parameter dict -> the nets, (C, A) read from its shapes (nets.infer_shape, as the packers do)."""
+        return cls(flat, *N.infer_shape(flat)[:cls.SHAPE_ARGS], device=device, dtype=dtype)
+
     def __init__(self, params: dict, obs_channels: int, num_actions: int = 24, device="cuda",
                  dtype=torch.float32, shapes: dict | None = None):
         self.C, self.A = int(obs_channels), int(num_actions)
@@ -1716,11 +1723,20 @@ class Learner:
     kernels at batch 128, so replaying them as one graph removes the launch overhead."""
 
     KEYS = ("observations", "actions", "rewards", "policies", "masks", "target_values", "discount_targets")
+    NETS = MuZeroNets
 
     def __init__(self, params: dict, obs_channels: int, num_actions: int = 24, unroll_steps: int = 10,
                  device="cuda", graph: bool = False, **opt):
+        self._setup(params, (obs_channels, num_actions), unroll_steps, device, graph, opt)
+
+    @classmethod
+    def from_params(cls, flat: dict, **kw):
+        """Any of the three learners from a flat parameter dict, (C, A) read from its shapes."""
+        return cls(flat, *N.infer_shape(flat)[:cls.NETS.SHAPE_ARGS], **kw)
+
+    def _setup(self, params, shape, unroll_steps, device, graph, opt):
         prefer_rocblas()
-        self.nets = MuZeroNets(params, obs_channels, num_actions, device)
+        self.nets = self.NETS(params, *shape, device=device)
         self.opt = AdamW(self.nets.parameters(), **opt)
         self.unroll_steps = int(unroll_steps)
         self.graph = bool(graph)
@@ -1736,9 +1752,6 @@ class Learner:
         self.opt.step()
         return {"total_loss": loss.detach(), "v_loss": v.detach(), "p_loss": pl.detach(), "d_loss": d.detach(),
                 "r_loss": r.detach()}
-
-    def _device_net(self, net):
-        return N.DeviceNet(self.nets.numpy(), net.C, net.A, device=net.buffer.device)
 
     def train_step(self, batch: dict) -> dict:
         if not self.graph:
@@ -1809,7 +1822,7 @@ class Learner:
 
     def push_to(self, net: "N.DeviceNet"):
         """Pack the current parameters into the self-play engine's arena (same layout) in place."""
-        fresh = self._device_net(net)
+        fresh = type(net).from_params(self.nets.numpy(), device=net.buffer.device)
         net.buffer.copy_(fresh.buffer)
         net.prepare()
 
@@ -1820,6 +1833,8 @@ CLASSIC_SCALING = dict(value=4.0, policy=2.0, chance=0.5, discount=1.0, reward=1
 
 class ClassicMuZeroNets(MuZeroNets):
     """Repr2 / Pred4 (A = 4) + StochasticDynamicsNetwork4 (muzero_classic_madn.py:314-408)."""
+
+    SHAPE_ARGS = 1
 
     def __init__(self, params: dict, obs_channels: int, device="cuda", dtype=torch.float32):
         from .stochastic import classic_param_shapes
@@ -1953,19 +1968,12 @@ class StochasticLearner(Learner):
     x0.5 @ 105 of 2500 steps) on batches of replay.VectorizedReplayBufferStochastic."""
 
     KEYS = Learner.KEYS + ("dice_outcomes", "dice_probs")
+    NETS = ClassicMuZeroNets
 
     def __init__(self, params: dict, obs_channels: int, unroll_steps: int = 10, device="cuda", graph: bool = False,
                  **opt):
         opt.setdefault("boundaries", CLASSIC_LR_BOUNDARIES)
-        prefer_rocblas()
-        self.nets = ClassicMuZeroNets(params, obs_channels, device)
-        self.opt = AdamW(self.nets.parameters(), **opt)
-        self.unroll_steps = int(unroll_steps)
-        self.graph = bool(graph)
-        self._g = None
-        self.sink = GradSink() if GROUPED_GRADS and torch.device(device).type == "cuda" else None
-        self.wt = WeightTranspose(self.nets.p) if FUSED_DENSE and FUSED_FWD and torch.device(device).type == "cuda" \
-            else None
+        self._setup(params, (obs_channels,), unroll_steps, device, graph, opt)
 
     def _step(self, batch):
         with _transposed(self.wt):
@@ -1975,10 +1983,6 @@ class StochasticLearner(Learner):
         return {"total_loss": loss.detach(), "v_loss": v.detach(), "p_loss": pl.detach(), "c_loss": c.detach(),
                 "d_loss": d.detach(), "r_loss": r.detach()}
 
-    def _device_net(self, net):
-        from .stochastic import DeviceClassicNet
-        return DeviceClassicNet(self.nets.numpy(), net.C, device=net.buffer.device)
-
 
 # ---- DOG: MuZero_DOG/train.py (its loss_fn / train_step, 24-164, are train_with_reward.py's) ------------------------
 class DogMuZeroNets(MuZeroNets):
@@ -1987,6 +1991,8 @@ class DogMuZeroNets(MuZeroNets):
     PredictionNetwork4 at A = 806 (the slice's definition; muzero_dog.py:85-99 are `pass`), on 34 x 56 observations.
     The 806-wide one-hot inputs (Dynamics Dense_0, Dense_6 / Dense_7's action rows) stay matrix products, as the
     reference computes them (66 MFLOP per step at batch 128 x 10, against ~10 GFLOP for the whole step)."""
+
+    SHAPE_ARGS = 0
 
     def __init__(self, params: dict, device="cuda", dtype=torch.float32):
         from . import muzero_dog as MD
@@ -2002,20 +2008,10 @@ class DogLearner(Learner):
     x0.2 @ 60, x0.5 @ 85 of 2500 steps, wd 1e-4; train.py:355-373) on the DOG nets, batches from a device ring at
     action_dim 806, obs (34, 56)."""
 
-    def __init__(self, params: dict, unroll_steps: int = 10, device="cuda", graph: bool = False, **opt):
-        prefer_rocblas()
-        self.nets = DogMuZeroNets(params, device)
-        self.opt = AdamW(self.nets.parameters(), **opt)
-        self.unroll_steps = int(unroll_steps)
-        self.graph = bool(graph)
-        self._g = None
-        self.sink = GradSink() if GROUPED_GRADS and torch.device(device).type == "cuda" else None
-        self.wt = WeightTranspose(self.nets.p) if FUSED_DENSE and FUSED_FWD and torch.device(device).type == "cuda" \
-            else None
+    NETS = DogMuZeroNets
 
-    def _device_net(self, net):
-        from .muzero_dog import DeviceDogNet
-        return DeviceDogNet(self.nets.numpy(), device=net.buffer.device)
+    def __init__(self, params: dict, unroll_steps: int = 10, device="cuda", graph: bool = False, **opt):
+        self._setup(params, (), unroll_steps, device, graph, opt)
 
 
 def train_loop(learner: Learner, engine, ring, iterations: int, train_steps: int, games_per_iteration: int,

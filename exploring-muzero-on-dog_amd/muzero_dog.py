@@ -17,8 +17,6 @@ restated by oracle/dog_muzero.py and checked against it (tests/test_gpu_dog_muze
 """
 from __future__ import annotations
 
-import ctypes
-
 import numpy as np
 import torch
 
@@ -40,31 +38,23 @@ def param_shapes() -> dict:
 
 
 def init_muzero_params(seed: int = 0) -> dict:
-    """init_muzero_params (muzero_dog.py:139-181) with Flax defaults (lecun_normal kernels, zero biases, unit LN
-    scales), seeded NumPy draws (jax threefry is not reproduced)."""
-    rng = np.random.default_rng(seed)
-    out = {}
-    for k, shp in param_shapes().items():
-        if k.endswith("kernel"):
-            fan_in = int(np.prod(shp[:-1]))
-            std = np.sqrt(1.0 / fan_in) / 0.87962566103423978
-            out[k] = (np.clip(rng.standard_normal(shp), -2.0, 2.0) * std).astype(np.float32)
-        elif k.endswith("scale"):
-            out[k] = np.ones(shp, np.float32)
-        else:
-            out[k] = np.zeros(shp, np.float32)
-    return out
+    """init_muzero_params (muzero_dog.py:139-181) with Flax defaults (nets.init_params)."""
+    return N.init_params(param_shapes(), seed)
 
 
 class DeviceDogNet(N._Packer):
     """Packed device copy of the slice's parameters + the ``muz_dog_net_w`` table the kernels read."""
 
+    TABLE = _L.MuzDogNetW
+    PREPARE, ROOT, RECURRENT = "muz_dog_net_prepare", "muz_dog_nets_root", "muz_dog_nets_recurrent"
+    SHAPE = (NUM_CHANNELS, NUM_ACTIONS)
+
     def __init__(self, params: dict, device="cuda"):
-        super().__init__(params, NUM_CHANNELS, NUM_ACTIONS)
+        self._pack(params, NUM_CHANNELS, NUM_ACTIONS, device)
+
+    def _spec(self):
         P, p = self.params, "prediction"
-        w = _L.MuzDogNetW()
-        w.obs_channels, w.num_actions = self.C, self.A
-        pred = self._pred_spec_no_logits()
+        pred = self._pred_spec(logits=False)
         k2, b2 = P[f"{p}/Dense_2/kernel"], P[f"{p}/Dense_2/bias"]
         logits = []
         for lo, hi in CHUNKS:
@@ -72,49 +62,19 @@ class DeviceDogNet(N._Packer):
             # chunks 0-2 packed for 256 columns (dense16<NT256>), the last for its 38 (dense16<nt_for(38)>)
             logits.append((self._put(N.pack_dense(kc, self.waves, N.nt_for(hi - lo, self.waves))), self._put(bc)))
         pred["d2"] = logits[0]
-        spec = {"repr": self._repr_spec(), "repr_ln7": self._ln("representation/LayerNorm_7"),
+        return {"repr": self._repr_spec(), "repr_ln7": self._ln("representation/LayerNorm_7"),
                 "dyn": self._dyn_spec(), "pred": pred, "logits": logits}
-        self._upload(w, spec, device)
-        self.prepare()
-
-    def _pred_spec_no_logits(self):
-        P, p = self.params, "prediction"
-        return dict(
-            ln0=self._ln(f"{p}/LayerNorm_0"), rb=[self._rb(f"{p}/ResBlock_{i}") for i in range(2)],
-            d03=self._dense_k(np.concatenate([P[f"{p}/Dense_0/kernel"], P[f"{p}/Dense_3/kernel"]], 1),
-                              np.concatenate([P[f"{p}/Dense_0/bias"], P[f"{p}/Dense_3/bias"]])),
-            ln1=self._ln(f"{p}/LayerNorm_1"), d1=self._dense(f"{p}/Dense_1"), ln2=self._ln(f"{p}/LayerNorm_2"),
-            ln3=self._ln(f"{p}/LayerNorm_3"), d4=self._dense(f"{p}/Dense_4"), d5=self._plain(f"{p}/Dense_5"))
-
-    def prepare(self):
-        with torch.cuda.device(self.buffer.device):
-            _L.check(_L.load().muz_dog_net_prepare(ctypes.byref(self.w), _L.stream_ptr()), "muz_dog_net_prepare")
 
 
-_NET_CACHE = []
+_NET_CACHE: dict = {}
 
 
 def as_device_net(params, device="cuda") -> DeviceDogNet:
-    """A flat ``net/Layer/param`` dict or a Flax tree (or a DeviceDogNet) -> DeviceDogNet.  New weights go into the
-    DeviceDogNet of the previous call in place (same arena layout), so an engine cached on it (game_agent_dog.
-    play_n_games_v3) keeps its buffers -- the reference's train loop passes a fresh params tree every iteration."""
-    if isinstance(params, DeviceDogNet):
-        return params
-    flat = params if all(isinstance(k, str) and "/" in k for k in params) else _flat(params)
-    flat = {k: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in flat.items()}
-    net = DeviceDogNet(flat, device=device)
-    prev = _NET_CACHE[0] if _NET_CACHE else None
-    if prev is not None and prev.buffer.shape == net.buffer.shape and prev.buffer.device == net.buffer.device:
-        prev.buffer.copy_(net.buffer)
-        prev.prepare()
-        return prev
-    _NET_CACHE[:] = [net]
-    return net
-
-
-def _flat(tree) -> dict:
-    from . import checkpoint as CK
-    return CK.muzero_tree_to_flat_any(tree)
+    """A flat ``net/Layer/param`` dict or a Flax tree (or a DeviceDogNet) -> DeviceDogNet (nets.cached_device_net).
+    New weights go into the DeviceDogNet of the previous call in place (same arena layout), so an engine cached on it
+    (game_agent_dog.play_n_games_v3) keeps its buffers -- the reference's train loop passes a fresh params tree every
+    iteration."""
+    return N.cached_device_net(_NET_CACHE, DeviceDogNet, params, device)
 
 
 def encode_board(env: DOG.DOGState, out: torch.Tensor | None = None) -> torch.Tensor:
@@ -125,40 +85,9 @@ def encode_board(env: DOG.DOGState, out: torch.Tensor | None = None) -> torch.Te
     return out
 
 
-def root_inference_fn(net: DeviceDogNet, observation: torch.Tensor, scratch: torch.Tensor | None = None):
-    """obs [B, 34, 56] -> (prior_logits [B, 806], value [B], embedding [B, 256])."""
-    lib = _L.load()
-    obs = observation.to(dtype=torch.float32).contiguous()
-    B = obs.shape[0]
-    if tuple(obs.shape[1:]) != (NUM_CHANNELS, 56):
-        raise ValueError(f"observation shape {tuple(obs.shape)} != (B, {NUM_CHANNELS}, 56)")
-    dev = obs.device
-    need = lib.muz_nets_root_scratch_bytes(B)
-    if scratch is None or _L.nbytes(scratch) < need:
-        scratch = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    logits = torch.empty((B, NUM_ACTIONS), dtype=torch.float32, device=dev)
-    value = torch.empty((B,), dtype=torch.float32, device=dev)
-    emb = torch.empty((B, LATENT), dtype=torch.float32, device=dev)
-    _L.check(lib.muz_dog_nets_root(net.w, _L.ptr(obs), B, _L.ptr(scratch), _L.nbytes(scratch), _L.ptr(logits),
-                                   _L.ptr(value), _L.ptr(emb), _L.stream_ptr()), "muz_dog_nets_root")
-    return logits, value, emb
-
-
-def recurrent_inference_fn(net: DeviceDogNet, action: torch.Tensor, embedding: torch.Tensor):
-    """(action [B], embedding [B, 256]) -> (reward, discount, prior_logits [B, 806], value, next_embedding)."""
-    lib = _L.load()
-    emb = embedding.to(dtype=torch.float32).contiguous()
-    act = action.to(device=emb.device, dtype=torch.int32).contiguous()
-    B, dev = emb.shape[0], emb.device
-    reward = torch.empty((B,), dtype=torch.float32, device=dev)
-    discount = torch.empty((B,), dtype=torch.float32, device=dev)
-    logits = torch.empty((B, NUM_ACTIONS), dtype=torch.float32, device=dev)
-    value = torch.empty((B,), dtype=torch.float32, device=dev)
-    nxt = torch.empty((B, LATENT), dtype=torch.float32, device=dev)
-    _L.check(lib.muz_dog_nets_recurrent(net.w, _L.ptr(act), _L.ptr(emb), B, _L.ptr(reward), _L.ptr(discount),
-                                        _L.ptr(logits), _L.ptr(value), _L.ptr(nxt), _L.stream_ptr()),
-             "muz_dog_nets_recurrent")
-    return reward, discount, logits, value, nxt
+# obs [B, 34, 56] -> (prior_logits [B, 806], value [B], embedding [B, 256]);
+# (action [B], embedding [B, 256]) -> (reward, discount, prior_logits [B, 806], value, next_embedding)
+root_inference_fn, recurrent_inference_fn = N.root_inference, N.recurrent_inference
 
 
 # ---------------------------------------------------------------------------------- search (muzero_dog.py:101-137)

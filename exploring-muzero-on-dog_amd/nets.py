@@ -7,6 +7,9 @@ Host side of the fused fp32 MFMA network kernels (csrc/nets.hip, csrc/nn.hpp):
   * ``DeviceNet`` packs the dense kernels into the MFMA B-fragment layout documented in
     include/muz.h, uploads everything as one device buffer and fills ``muz_net_w``;
   * ``root_inference_fn`` / ``recurrent_inference_fn`` mirror lines 621-661.
+The classic (stochastic.py) and DOG (muzero_dog.py) networks are built from the same pieces: ``init_params``,
+``flat_f32`` / ``infer_shape``, ``_Packer`` (``from_params``, ``prepare``), ``root_inference`` / ``recurrent_inference``
+and ``cached_device_net``; each of those modules adds its shape table, its ``_spec`` and its entry-point names.
 """
 from __future__ import annotations
 
@@ -66,21 +69,45 @@ def param_shapes(obs_channels: int, num_actions: int = 24) -> dict:
     return s
 
 
-def init_muzero_params(seed: int, obs_channels: int, num_actions: int = 24) -> dict:
-    """init_muzero_params (lines 706-748) with Flax defaults: lecun_normal kernels (truncated at 2 std),
-    zero biases, unit LayerNorm scales.  Seeded NumPy draws (jax threefry is not reproduced)."""
+def init_params(shapes: dict, seed: int) -> dict:
+    """Flax defaults for a flat shape table: lecun_normal kernels (truncated at 2 std), zero biases, unit LayerNorm
+    scales.  Seeded NumPy draws in the table's order (jax threefry is not reproduced)."""
     rng = np.random.default_rng(seed)
     out = {}
-    for k, shp in param_shapes(obs_channels, num_actions).items():
+    for k, shp in shapes.items():
         if k.endswith("kernel"):
-            fan_in = int(np.prod(shp[:-1]))
-            std = math.sqrt(1.0 / fan_in) / 0.87962566103423978
+            std = math.sqrt(1.0 / int(np.prod(shp[:-1]))) / 0.87962566103423978
             out[k] = (np.clip(rng.standard_normal(shp), -2.0, 2.0) * std).astype(np.float32)
-        elif k.endswith("scale"):
-            out[k] = np.ones(shp, np.float32)
         else:
-            out[k] = np.zeros(shp, np.float32)
+            out[k] = (np.ones if k.endswith("scale") else np.zeros)(shp, np.float32)
     return out
+
+
+def init_muzero_params(seed: int, obs_channels: int, num_actions: int = 24) -> dict:
+    """init_muzero_params (lines 706-748) with Flax defaults (init_params)."""
+    return init_params(param_shapes(obs_channels, num_actions), seed)
+
+
+def flat_tree(params) -> dict:
+    """Reference params -> flat ``{"net/Layer/param": leaf}``, the leaves as they are: init_muzero_params' nested Flax
+    tree (``{"representation": {"params": ...}, "dynamics": ..., "prediction": ...}``) or an already flat dict."""
+    if isinstance(params, dict) and all(isinstance(k, str) and "/" in k for k in params):
+        return params
+    from . import checkpoint as CK
+    return CK.muzero_tree_to_flat_any(params)
+
+
+def flat_f32(params) -> dict:
+    """flat_tree with every leaf (torch, on any device, or NumPy) as a host float32 ndarray."""
+    return {k: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32)
+            for k, v in flat_tree(params).items()}
+
+
+def infer_shape(flat: dict, obs_channels: int | None = None) -> tuple:
+    """(C, A) of a flat parameter dict: the representation's Dense_1 takes the C - 6 non-board channels, the
+    prediction's Dense_2 gives the A logits."""
+    C = int(flat["representation/Dense_1/kernel"].shape[0]) + 6 if obs_channels is None else int(obs_channels)
+    return C, int(flat["prediction/Dense_2/kernel"].shape[1])
 
 
 # ---------------------------------------------------------------------------------- packing
@@ -106,14 +133,44 @@ def pack_dense(W: np.ndarray, nw: int, nt: int) -> np.ndarray:
 
 class _Packer:
     """Builds one device buffer of packed parameters and fills a ctypes weight table from a nested spec
-    (leaf = offset in floats, (w, b) pair = muz_dense / muz_ln, list = array field, dict = sub-struct)."""
+    (leaf = offset in floats, (w, b) pair = muz_dense / muz_ln, list = array field, dict = sub-struct).
 
-    def __init__(self, params: dict, obs_channels: int, num_actions: int):
+    A subclass names its weight table, its C entry points and, where the game fixes them, its (C, A); ``_spec`` lays
+    the parameters out.  Its constructor and ``from_params`` both end in ``_pack``."""
+
+    TABLE = None                          # the ctypes weight table (include/muz.h)
+    PREPARE = ROOT = RECURRENT = None     # C entry points (lib.SIGNATURES)
+    SHAPE = (None, None)                  # (C, A) where the game fixes one
+
+    @classmethod
+    def from_params(cls, flat: dict, device="cuda", obs_channels: int | None = None, prepare: bool = True):
+        """A flat parameter dict -> the packed net, (C, A) read from its shapes (infer_shape).  prepare=False stops
+        after the upload (the host layout alone, no kernel)."""
+        net = cls.__new__(cls)
+        net._pack(flat, *infer_shape(flat, obs_channels), device, prepare)
+        return net
+
+    def _pack(self, params: dict, obs_channels: int, num_actions: int, device, prepare: bool = True):
         self.C, self.A = int(obs_channels), int(num_actions)
+        if any(want is not None and want != got for want, got in zip(self.SHAPE, (self.C, self.A))):
+            raise ValueError(f"{type(self).__name__}: (C, A) = {(self.C, self.A)} != {self.SHAPE}")
         self.waves = _L.load().muz_tile_waves()   # column groups of the packed 16-row layers (csrc/nn.hpp kWaves)
         self._chunks = []
         self._off = 0
         self.params = {k: np.asarray(v, np.float32) for k, v in params.items()}
+        self.w = self.TABLE()
+        self.w.obs_channels, self.w.num_actions = self.C, self.A
+        self.spec = self._spec()
+        self.buffer = torch.from_numpy(np.concatenate(self._chunks)).to(device)
+        self._fill(self.w, self.spec, self.buffer.data_ptr())
+        if prepare:
+            self.prepare()
+
+    def prepare(self):
+        """Re-derive the FiLM tables from the packed weights (after they change in place, e.g. a parameter
+        broadcast from the learner)."""
+        with torch.cuda.device(self.buffer.device):
+            _L.check(getattr(_L.load(), self.PREPARE)(ctypes.byref(self.w), _L.stream_ptr()), self.PREPARE)
 
     def _put(self, arr) -> int:
         a = np.ascontiguousarray(np.asarray(arr, np.float32).reshape(-1))
@@ -154,15 +211,18 @@ class _Packer:
             ln5=self._ln(f"{r}/LayerNorm_5"), d3=self._dense(f"{r}/Dense_3"), ln6=self._ln(f"{r}/LayerNorm_6"),
             rb=[self._rb(f"{r}/ResBlock_{i}") for i in range(6)], d4=self._dense(f"{r}/Dense_4"))
 
-    def _pred_spec(self):
+    def _pred_spec(self, logits: bool = True):
+        """PredictionNetwork4; logits=False leaves Dense_2 (``d2``) to the caller (DOG packs it in column chunks)."""
         P, p = self.params, "prediction"
-        return dict(
+        spec = dict(
             ln0=self._ln(f"{p}/LayerNorm_0"), rb=[self._rb(f"{p}/ResBlock_{i}") for i in range(2)],
             d03=self._dense_k(np.concatenate([P[f"{p}/Dense_0/kernel"], P[f"{p}/Dense_3/kernel"]], 1),
                               np.concatenate([P[f"{p}/Dense_0/bias"], P[f"{p}/Dense_3/bias"]])),
-            ln1=self._ln(f"{p}/LayerNorm_1"), d1=self._dense(f"{p}/Dense_1"), ln2=self._ln(f"{p}/LayerNorm_2"),
-            d2=self._dense(f"{p}/Dense_2"), ln3=self._ln(f"{p}/LayerNorm_3"), d4=self._dense(f"{p}/Dense_4"),
-            d5=self._plain(f"{p}/Dense_5"))
+            ln1=self._ln(f"{p}/LayerNorm_1"), d1=self._dense(f"{p}/Dense_1"), ln2=self._ln(f"{p}/LayerNorm_2"))
+        if logits:
+            spec["d2"] = self._dense(f"{p}/Dense_2")
+        spec.update(ln3=self._ln(f"{p}/LayerNorm_3"), d4=self._dense(f"{p}/Dense_4"), d5=self._plain(f"{p}/Dense_5"))
+        return spec
 
     def _dyn_spec(self):
         """DynamicsNetwork4 (lines 391-457); the FiLM table [A + 1][512] is derived on the device (prepare)."""
@@ -180,12 +240,6 @@ class _Packer:
             d67_onehot=put(np.concatenate([k6[LATENT:LATENT + A], k7[LATENT:LATENT + A]], 1)),
             reward_head=self._plain(f"{d}/reward_head"), discount_head=self._plain(f"{d}/discount_head"),
             film=put(np.zeros((A + 1) * 2 * LATENT, np.float32)))
-
-    def _upload(self, w, spec, device):
-        host = np.concatenate(self._chunks) if self._chunks else np.zeros(4, np.float32)
-        self.buffer = torch.from_numpy(host).to(device)
-        self._fill(w, spec, self.buffer.data_ptr())
-        self.w = w
 
     @staticmethod
     def _fill(struct, spec, base):
@@ -213,57 +267,54 @@ class _Packer:
 class DeviceNet(_Packer):
     """Packed device copy of a det-MADN parameter dict + the ``muz_net_w`` table the kernels read."""
 
-    def __init__(self, params: dict, obs_channels: int, num_actions: int = 24, device="cuda"):
-        super().__init__(params, obs_channels, num_actions)
-        w = MuzNetW()
-        w.obs_channels, w.num_actions = self.C, self.A
-        spec = {"repr": self._repr_spec(), "dyn": self._dyn_spec(), "pred": self._pred_spec()}
-        self._upload(w, spec, device)
-        self.prepare()
+    TABLE = MuzNetW
+    PREPARE, ROOT, RECURRENT = "muz_net_prepare", "muz_nets_root", "muz_nets_recurrent"
 
-    def prepare(self):
-        """Re-derive the per-action FiLM table from the packed weights (after they change in place, e.g.
-        a parameter broadcast from the learner)."""
-        with torch.cuda.device(self.buffer.device):
-            _L.check(_L.load().muz_net_prepare(ctypes.byref(self.w), _L.stream_ptr()), "muz_net_prepare")
+    def __init__(self, params: dict, obs_channels: int, num_actions: int = 24, device="cuda"):
+        self._pack(params, obs_channels, num_actions, device)
+
+    def _spec(self):
+        return {"repr": self._repr_spec(), "dyn": self._dyn_spec(), "pred": self._pred_spec()}
 
 
 # ---------------------------------------------------------------------------------- inference
-def root_inference_fn(net: DeviceNet, observation: torch.Tensor, scratch: torch.Tensor | None = None):
-    """root_inference_fn (lines 621-630): obs [B, C, 56] -> (prior_logits [B, A], value [B], embedding [B, 256])."""
+def root_inference(net: _Packer, observation: torch.Tensor, scratch: torch.Tensor | None = None):
+    """root_inference_fn (lines 621-630) of any of the three games' nets (``net.ROOT``): obs [B, C, 56] ->
+    (prior_logits [B, A], value [B], embedding [B, 256])."""
     lib = _L.load()
     obs = observation.to(dtype=torch.float32).contiguous()
-    B = obs.shape[0]
-    if obs.shape[1] != net.C or obs.shape[2] != 56:
+    B, dev = obs.shape[0], obs.device
+    if tuple(obs.shape[1:]) != (net.C, 56):
         raise ValueError(f"observation shape {tuple(obs.shape)} != (B, {net.C}, 56)")
-    dev = obs.device
     need = lib.muz_nets_root_scratch_bytes(B)
-    if scratch is None or scratch.numel() * scratch.element_size() < need:
+    if scratch is None or _L.nbytes(scratch) < need:
         scratch = torch.empty(need // 4, dtype=torch.float32, device=dev)
     logits = torch.empty((B, net.A), dtype=torch.float32, device=dev)
     value = torch.empty((B,), dtype=torch.float32, device=dev)
     emb = torch.empty((B, LATENT), dtype=torch.float32, device=dev)
-    _L.check(lib.muz_nets_root(net.w, _L.ptr(obs), B, _L.ptr(scratch), _L.nbytes(scratch), _L.ptr(logits),
-                               _L.ptr(value), _L.ptr(emb), _L.stream_ptr()), "muz_nets_root")
+    _L.check(getattr(lib, net.ROOT)(net.w, _L.ptr(obs), B, _L.ptr(scratch), _L.nbytes(scratch), _L.ptr(logits),
+                                    _L.ptr(value), _L.ptr(emb), _L.stream_ptr()), net.ROOT)
     return logits, value, emb
 
 
-def recurrent_inference_fn(net: DeviceNet, action: torch.Tensor, embedding: torch.Tensor):
-    """recurrent_inference_fn (lines 632-661) -> (reward, discount, prior_logits, value, next_embedding)."""
-    lib = _L.load()
+def recurrent_inference(net: _Packer, action: torch.Tensor, embedding: torch.Tensor):
+    """recurrent_inference_fn (lines 632-661) of the det or the DOG net (``net.RECURRENT``) ->
+    (reward, discount, prior_logits [B, A], value, next_embedding)."""
     emb = embedding.to(dtype=torch.float32).contiguous()
     act = action.to(device=emb.device, dtype=torch.int32).contiguous()
-    B = emb.shape[0]
-    dev = emb.device
+    B, dev = emb.shape[0], emb.device
     reward = torch.empty((B,), dtype=torch.float32, device=dev)
     discount = torch.empty((B,), dtype=torch.float32, device=dev)
     logits = torch.empty((B, net.A), dtype=torch.float32, device=dev)
     value = torch.empty((B,), dtype=torch.float32, device=dev)
     nxt = torch.empty((B, LATENT), dtype=torch.float32, device=dev)
-    _L.check(lib.muz_nets_recurrent(net.w, _L.ptr(act), _L.ptr(emb), B, _L.ptr(reward), _L.ptr(discount),
-                                    _L.ptr(logits), _L.ptr(value), _L.ptr(nxt), _L.stream_ptr()),
-             "muz_nets_recurrent")
+    _L.check(getattr(_L.load(), net.RECURRENT)(net.w, _L.ptr(act), _L.ptr(emb), B, _L.ptr(reward), _L.ptr(discount),
+                                               _L.ptr(logits), _L.ptr(value), _L.ptr(nxt), _L.stream_ptr()),
+             net.RECURRENT)
     return reward, discount, logits, value, nxt
+
+
+root_inference_fn, recurrent_inference_fn = root_inference, recurrent_inference
 
 
 # ---------------------------------------------------------------------------------- reference params
@@ -282,36 +333,41 @@ def rng_key_to_seed(rng_key) -> int:
     return int((int(k[0]) << 32) | int(k[1]))
 
 
-def as_device_net(params, obs_channels: int | None = None, device="cuda") -> DeviceNet:
-    """The reference's ``params`` argument -> a DeviceNet (packed once, cached per params object).
+def _device_of(device) -> torch.device:
+    """torch.device(device) as a tensor's ``.device`` states it: "cuda" is the current device, "cuda:0"."""
+    d = torch.device(device)
+    return torch.device(d.type, torch.cuda.current_device()) if d.type == "cuda" and d.index is None else d
 
-    Accepts what the reference passes around -- init_muzero_params' nested Flax tree
-    (``{"representation": {"params": ...}, "dynamics": ..., "prediction": ...}``,
-    muzero_deterministic_madn.py:706-748), a flat ``"net/Layer/param"`` dict, or a DeviceNet.  The channel
-    count is read from the representation's Dense_1 kernel (C - 6 inputs) when not given."""
-    if isinstance(params, DeviceNet):
+
+def cached_device_net(cache: dict, cls, params, device="cuda", obs_channels: int | None = None):
+    """The reference's ``params`` argument -> a ``cls`` net, packed once per params object: ``cache`` (one per game)
+    holds the one live weight set, which is what the reference's loops use.  Accepts what the reference passes around
+    -- init_muzero_params' nested Flax tree, a flat ``"net/Layer/param"`` dict -- or a ``cls`` net.  An in-place
+    update of the same tree re-packs (params_fingerprint)."""
+    if isinstance(params, cls):
         return params
     fp = params_fingerprint(params)
-    hit = _NET_CACHE.get(id(params))
-    if hit is not None and hit[0] is params and hit[2] == fp and str(hit[1].buffer.device) == str(torch.device(device)):
+    hit = cache.get(id(params))
+    if hit is not None and hit[0] is params and hit[2] == fp and hit[1].buffer.device == _device_of(device):
         return hit[1]
-    from . import checkpoint as CK
-    flat = params if all(isinstance(k, str) and "/" in k for k in params) else CK.muzero_tree_to_flat_any(params)
-    flat = {k: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in flat.items()}
-    C = int(flat["representation/Dense_1/kernel"].shape[0]) + 6 if obs_channels is None else int(obs_channels)
-    A = int(flat["prediction/Dense_2/kernel"].shape[1])
-    net = DeviceNet(flat, C, A, device=device)
-    prev = next(iter(_NET_CACHE.values()), None)
-    if prev is not None and (prev[1].C, prev[1].A) == (C, A) and prev[1].buffer.shape == net.buffer.shape \
+    net = cls.from_params(flat_f32(params), device, obs_channels)
+    prev = next(iter(cache.values()), None)
+    if prev is not None and (prev[1].C, prev[1].A) == (net.C, net.A) and prev[1].buffer.shape == net.buffer.shape \
             and prev[1].buffer.device == net.buffer.device:
-        # same shapes: the new weights go into the live DeviceNet, so engines cached on it (game_agent.cached_engine)
-        # keep their state, workspace and buffers across a training loop's iterations
+        # same shapes: the new weights go into the live net, so engines cached on it (game_agent.cached_engine) keep
+        # their state, workspace and buffers across a training loop's iterations
         prev[1].buffer.copy_(net.buffer)
         prev[1].prepare()
         net = prev[1]
-    _NET_CACHE.clear()          # one live weight set per process is what the reference's loops use
-    _NET_CACHE[id(params)] = (params, net, fp)
+    cache.clear()
+    cache[id(params)] = (params, net, fp)
     return net
+
+
+def as_device_net(params, obs_channels: int | None = None, device="cuda") -> DeviceNet:
+    """cached_device_net for det-MADN: the channel count is read from the representation's Dense_1 kernel (C - 6
+    inputs) when not given."""
+    return cached_device_net(_NET_CACHE, DeviceNet, params, device, obs_channels)
 
 
 _VERSIONED = {}    # id(tree) -> (tree, version()): trees whose owner updates the leaves in place

@@ -14,18 +14,22 @@ import numpy as np
 import torch
 
 from . import lib as _L
-from .nets import LATENT, _Packer
+from .nets import LATENT, _Packer, cached_device_net, init_params, root_inference
 
 A_CLASSIC = 4
 CHANCE = 6
 
 
 class DeviceClassicNet(_Packer):
+    TABLE = _L.MuzClassicNetW
+    PREPARE, ROOT = "muz_classic_net_prepare", "muz_classic_nets_root"    # the action / chance FiLM tables; root
+    SHAPE = (None, A_CLASSIC)
+
     def __init__(self, params: dict, obs_channels: int, device="cuda"):
-        super().__init__(params, obs_channels, A_CLASSIC)
+        self._pack(params, obs_channels, A_CLASSIC, device)
+
+    def _spec(self):
         P, put, A, d = self.params, self._put, self.A, "dynamics"
-        w = _L.MuzClassicNetW()
-        w.obs_channels, w.num_actions = self.C, self.A
         rd = P[f"{d}/reward_dense/kernel"]
 
         def cat(n1, n2):
@@ -52,14 +56,7 @@ class DeviceClassicNet(_Packer):
             chance_proj=self._dense(f"{d}/chance_proj"),
             act_film_tab=put(np.zeros((A + 1) * 2 * LATENT, np.float32)),
             chance_film_tab=put(np.zeros((CHANCE + 1) * 2 * LATENT, np.float32)))
-        self._upload(w, spec, device)
-        self.prepare()
-
-    def prepare(self):
-        """Re-derive the action / chance FiLM tables from the packed weights."""
-        with torch.cuda.device(self.buffer.device):
-            _L.check(_L.load().muz_classic_net_prepare(ctypes.byref(self.w), _L.stream_ptr()),
-                     "muz_classic_net_prepare")
+        return spec
 
 
 def classic_param_shapes(obs_channels: int, num_actions: int = A_CLASSIC, chance_outcomes: int = 6) -> dict:
@@ -88,39 +85,15 @@ def classic_param_shapes(obs_channels: int, num_actions: int = A_CLASSIC, chance
 
 
 def init_classic_params(obs_channels: int, seed: int = 0) -> dict:
-    """Flax-default initialisation (lecun_normal kernels truncated at 2 std, zero biases, unit LayerNorm
-    scales) from seeded NumPy draws, in classic_param_shapes order."""
-    rng = np.random.default_rng(seed)
-    out = {}
-    for k, shp in classic_param_shapes(obs_channels).items():
-        if k.endswith("kernel"):
-            std = np.sqrt(1.0 / int(np.prod(shp[:-1]))) / 0.87962566103423978
-            out[k] = (np.clip(rng.standard_normal(shp), -2.0, 2.0) * std).astype(np.float32)
-        else:
-            out[k] = (np.ones(shp) if k.endswith("scale") else np.zeros(shp)).astype(np.float32)
-    return out
+    """Flax-default initialisation (nets.init_params) in classic_param_shapes order."""
+    return init_params(classic_param_shapes(obs_channels), seed)
 
 
 def _f32(t):
     return t.to(dtype=torch.float32).contiguous()
 
 
-def root_inference_fn(net: DeviceClassicNet, observation: torch.Tensor, scratch: torch.Tensor | None = None):
-    """root_inference_fn (453-462): obs [B, 2P+3, 56] -> (prior_logits [B, 4], value [B], embedding [B, 256])."""
-    lib = _L.load()
-    obs = _f32(observation)
-    B, dev = obs.shape[0], obs.device
-    if obs.shape[1] != net.C or obs.shape[2] != 56:
-        raise ValueError(f"observation shape {tuple(obs.shape)} != (B, {net.C}, 56)")
-    need = lib.muz_nets_root_scratch_bytes(B)
-    if scratch is None or _L.nbytes(scratch) < need:
-        scratch = torch.empty(need // 4, dtype=torch.float32, device=dev)
-    logits = torch.empty((B, A_CLASSIC), dtype=torch.float32, device=dev)
-    value = torch.empty((B,), dtype=torch.float32, device=dev)
-    emb = torch.empty((B, LATENT), dtype=torch.float32, device=dev)
-    _L.check(lib.muz_classic_nets_root(net.w, _L.ptr(obs), B, _L.ptr(scratch), _L.nbytes(scratch), _L.ptr(logits),
-                                       _L.ptr(value), _L.ptr(emb), _L.stream_ptr()), "muz_classic_nets_root")
-    return logits, value, emb
+root_inference_fn = root_inference      # (453-462): obs [B, 2P+3, 56] -> (prior_logits [B, 4], value [B], embedding)
 
 
 def decision_recurrent_fn(net: DeviceClassicNet, action: torch.Tensor, embedding: torch.Tensor):
@@ -203,29 +176,8 @@ _NET_CACHE: dict = {}
 
 def as_device_classic_net(params, obs_channels: int | None = None, device="cuda") -> DeviceClassicNet:
     """The reference's classic ``params`` (init_muzero_params' nested Flax tree, muzero_classic_madn.py, or a
-    flat dict, or a DeviceClassicNet) -> DeviceClassicNet, packed once per params object."""
-    if isinstance(params, DeviceClassicNet):
-        return params
-    from .nets import params_fingerprint
-    fp = params_fingerprint(params)          # an in-place update of the same tree re-packs (nets.as_device_net)
-    hit = _NET_CACHE.get(id(params))
-    if hit is not None and hit[0] is params and hit[2] == fp and str(hit[1].buffer.device) == str(torch.device(device)):
-        return hit[1]
-    from . import checkpoint as CK
-    flat = params if all(isinstance(k, str) and "/" in k for k in params) else CK.muzero_tree_to_flat_any(params)
-    flat = {k: np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v, np.float32) for k, v in flat.items()}
-    C = int(flat["representation/Dense_1/kernel"].shape[0]) + 6 if obs_channels is None else int(obs_channels)
-    net = DeviceClassicNet(flat, C, device=device)
-    prev = next(iter(_NET_CACHE.values()), None)
-    if prev is not None and prev[1].C == C and prev[1].buffer.shape == net.buffer.shape \
-            and prev[1].buffer.device == net.buffer.device:
-        # same shapes: new weights into the live net, so the cached self-play engine keeps its buffers
-        prev[1].buffer.copy_(net.buffer)
-        prev[1].prepare()
-        net = prev[1]
-    _NET_CACHE.clear()
-    _NET_CACHE[id(params)] = (params, net, fp)
-    return net
+    flat dict, or a DeviceClassicNet) -> DeviceClassicNet, packed once per params object (nets.cached_device_net)."""
+    return cached_device_net(_NET_CACHE, DeviceClassicNet, params, device, obs_channels)
 
 
 def run_stochastic_muzero_mcts(params, rng_key, observations, invalid_actions, num_simulations, max_depth,

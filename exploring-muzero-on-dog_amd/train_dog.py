@@ -57,17 +57,10 @@ LR_BOUNDARIES = LR.DET_LR_BOUNDARIES        # :355-363 (30 / 60 / 85 iterations:
 INPUT_SHAPE = (MD.NUM_CHANNELS, 56)         # encode_board of a 4-player reset (:186-205)
 
 
-class _DogOptimizer(T.Optimizer):
-    def init(self, params) -> T.OptState:
-        flat = {k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in T._flat(params).items()}
-        return T.OptState(LR.DogLearner(flat, unroll_steps=self.unroll_steps, graph=self.graph, lr0=self.lr0,
-                                        steps_per_iteration=self.spi, boundaries=self.boundaries))
-
-
 def make_optimizer(cfg: dict) -> T.Optimizer:
     """optax.chain(clip_by_global_norm(5.0), adamw(piecewise_constant_schedule, weight_decay=1e-4)) (:355-373)."""
-    return _DogOptimizer(LR.DogLearner, cfg["unroll_steps"], cfg["learning_rate"], cfg["train_steps_per_iteration"],
-                         LR_BOUNDARIES)
+    return T.Optimizer(LR.DogLearner, cfg["unroll_steps"], cfg["learning_rate"], cfg["train_steps_per_iteration"],
+                       LR_BOUNDARIES)
 
 
 optimizer = make_optimizer(config)
@@ -93,9 +86,7 @@ def init_muzero_params(rng_key, input_shape=INPUT_SHAPE) -> dict:
 
 def loss_fn(params, batch):
     """:24-146 -> (total_loss, (value_loss, policy_loss, discount_loss, reward_loss)) on the batch's device."""
-    flat = T._flat(params)
-    nets = LR.DogMuZeroNets({k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in flat.items()},
-                            device=batch["observations"].device)
+    nets = LR.DogMuZeroNets.from_params(N.flat_f32(params), device=batch["observations"].device)
     return LR.loss_fn(nets, batch, config["unroll_steps"])
 
 
@@ -123,7 +114,7 @@ def test_training(config, params=None, opt_state=None, log=print):
     bootstrap switch, self-play of ``num_games_per_iteration`` DOG games (game_agent_dog.play_n_games_v3), the games
     saved into the ring, ``train_steps_per_iteration`` learner steps, a checkpoint every 100 iterations."""
     opt = make_optimizer(config) if opt_state is None else None
-    return T.run_training(config, params, opt_state, kind="dog", play_n_games_v3=GAD.play_n_games_v3,
+    return T.run_training(config, params, opt_state, play_n_games_v3=GAD.play_n_games_v3,
                           make_replay=_replay, optimizer=opt if opt is not None else optimizer,
                           init_params=init_muzero_params, input_shape=INPUT_SHAPE, schedule=TEMPERATURE_SCHEDULE,
                           switch_guard=lambda cfg: True, checkpoint_names=_checkpoint_names, log=log)

@@ -19,6 +19,7 @@ import torch
 from . import classic as E
 from . import game_agent_stochastic as GS
 from . import learner as LR
+from . import nets as N
 from . import replay as R
 from . import stochastic as ST
 from . import training as T
@@ -93,16 +94,12 @@ def balanced_loss(ce, is_rare, mask, n_valid, w_rare=1.0, w_common=0.1):
 def init_muzero_params(rng_key, input_shape) -> dict:
     """muzero_classic_madn.py:519-565: the Flax tree for an observation of ``input_shape`` = (C, 56)."""
     from . import checkpoint as CK
-    from .nets import rng_key_to_seed
-    return CK.flat_to_muzero_tree(ST.init_classic_params(int(input_shape[0]), rng_key_to_seed(rng_key) % (2 ** 32)))
+    return CK.flat_to_muzero_tree(ST.init_classic_params(int(input_shape[0]), N.rng_key_to_seed(rng_key) % (2 ** 32)))
 
 
 def loss_fn_stochastic(params, batch):
     """:34-181 -> (total, (value, policy, chance, discount, reward)) on the batch's device."""
-    flat = T._flat(params)
-    nets = LR.ClassicMuZeroNets({k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in flat.items()},
-                                int(flat["representation/Dense_1/kernel"].shape[0]) + 6,
-                                device=batch["observations"].device)
+    nets = LR.ClassicMuZeroNets.from_params(N.flat_f32(params), device=batch["observations"].device)
     return LR.loss_fn_stochastic(nets, batch, config["unroll_steps"])
 
 
@@ -130,7 +127,7 @@ def test_training(config, params=None, opt_state=None, log=print):
     """:201-355 -> (params, opt_state, times_per_iteration)."""
     opt = make_optimizer(config) if opt_state is None else optimizer
     input_shape = (E.num_channels(4), E.CELLS)          # :218-239: encode_board of a 4-player reset (11, 56)
-    return T.run_training(config, params, opt_state, kind="classic", play_n_games_v3=GS.play_n_games_v3,
+    return T.run_training(config, params, opt_state, play_n_games_v3=GS.play_n_games_v3,
                           make_replay=_replay, optimizer=opt, init_params=init_muzero_params,
                           input_shape=input_shape, schedule=TEMPERATURE_SCHEDULE,
                           switch_guard=lambda cfg: not cfg["Bootstrap_Value_Target"],

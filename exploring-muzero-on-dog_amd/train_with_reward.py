@@ -96,11 +96,7 @@ def init_muzero_params(rng_key, input_shape) -> dict:
 
 def loss_fn(params, batch):
     """:24-146 -> (total_loss, (value_loss, policy_loss, discount_loss, reward_loss)) on the batch's device."""
-    flat = T._flat(params)
-    dev = batch["observations"].device
-    nets = LR.MuZeroNets({k: (v.detach().cpu().numpy() if hasattr(v, "detach") else v) for k, v in flat.items()},
-                         int(flat["representation/Dense_1/kernel"].shape[0]) + 6,
-                         int(flat["prediction/Dense_2/kernel"].shape[1]), device=dev)
+    nets = LR.MuZeroNets.from_params(N.flat_f32(params), device=batch["observations"].device)
     return LR.loss_fn(nets, batch, config["unroll_steps"])
 
 
@@ -144,8 +140,7 @@ def test_training(config, params=None, opt_state=None, log=print):
     opt = make_optimizer(config) if opt_state is None else None
     input_shape = (E.num_channels(4), E.CELLS)          # :186-205: encode_board of a 4-player reset
     # (self-play uses game_agent's own RULES, as the reference's play_n_games_v3 does)
-    return T.run_training(config, params, opt_state, kind="det", play_n_games_v3=play,
-                          make_replay=_replay,
+    return T.run_training(config, params, opt_state, play_n_games_v3=play, make_replay=_replay,
                           optimizer=opt if opt is not None else optimizer, init_params=init_muzero_params,
                           input_shape=input_shape, schedule=TEMPERATURE_SCHEDULE,
                           switch_guard=lambda cfg: True, checkpoint_names=_checkpoint_names, log=log)

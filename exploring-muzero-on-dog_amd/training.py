@@ -25,12 +25,7 @@ import torch
 
 from . import checkpoint as CK
 from . import learner as LR
-
-
-def _flat(params) -> dict:
-    if isinstance(params, dict) and all(isinstance(k, str) and "/" in k for k in params):
-        return params
-    return CK.muzero_tree_to_flat_any(params)
+from . import nets as N
 
 
 class OptState:
@@ -41,7 +36,6 @@ class OptState:
         self.learner = learner
         self.tree = CK.flat_to_muzero_tree(learner.nets.p)      # leaves: the live parameter tensors
         self.version = 0                                        # in-place updates of the tree so far
-        from . import nets as N
         N.register_versioned_params(self.tree, lambda: self.version)
 
     @property
@@ -53,7 +47,7 @@ class OptState:
         if params is self.tree:
             return
         self.version += 1
-        flat = _flat(params)
+        flat = N.flat_tree(params)
         if set(flat) != set(self.learner.nets.p):
             raise ValueError("params do not match the learner's parameter names")
         with torch.no_grad():
@@ -84,22 +78,15 @@ class Optimizer:
     with ``init(params) -> OptState`` (train_with_reward.py:361-373, train_stochastic.py:416-428)."""
 
     def __init__(self, learner_cls, unroll_steps: int, learning_rate: float, steps_per_iteration: int,
-                 boundaries, graph: bool = True):
+                 boundaries, graph: bool = True, device="cuda"):
         self.learner_cls, self.unroll_steps = learner_cls, int(unroll_steps)
         self.lr0, self.spi, self.boundaries = float(learning_rate), int(steps_per_iteration), tuple(boundaries)
-        self.graph = bool(graph)
+        self.graph, self.device = bool(graph), device
 
     def init(self, params) -> OptState:
-        flat = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32))
-                for k, v in _flat(params).items()}
-        C = int(flat["representation/Dense_1/kernel"].shape[0]) + 6
-        kw = dict(unroll_steps=self.unroll_steps, graph=self.graph, lr0=self.lr0, steps_per_iteration=self.spi,
-                  boundaries=self.boundaries)
-        if self.learner_cls is LR.Learner:
-            learner = LR.Learner(flat, C, int(flat["prediction/Dense_2/kernel"].shape[1]), **kw)
-        else:
-            learner = self.learner_cls(flat, C, **kw)
-        return OptState(learner)
+        return OptState(self.learner_cls.from_params(
+            N.flat_f32(params), unroll_steps=self.unroll_steps, device=self.device, graph=self.graph, lr0=self.lr0,
+            steps_per_iteration=self.spi, boundaries=self.boundaries))
 
     def schedule(self, step: int) -> float:
         """optax.piecewise_constant_schedule(lr, {b * steps_per_iteration: s})."""
@@ -140,9 +127,7 @@ def save_checkpoint(params_path: str, opt_path: str, params, opt_state: OptState
     flax.serialization.from_bytes) and opt_state to a msgpack map {count, mu, nu} of the same encoding."""
     os.makedirs(os.path.dirname(params_path) or ".", exist_ok=True)
     os.makedirs(os.path.dirname(opt_path) or ".", exist_ok=True)
-    flat = {k: (v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, np.float32))
-            for k, v in _flat(params).items()}
-    CK.save_flax_msgpack(params_path, CK.flat_to_muzero_tree(flat))
+    CK.save_flax_msgpack(params_path, CK.flat_to_muzero_tree(N.flat_f32(params)))
     sd = opt_state.state_dict()
     with open(opt_path, "wb") as f:
         f.write(CK.dumps_flax_msgpack({"count": np.asarray(sd["count"], np.int32),
@@ -161,7 +146,7 @@ def load_checkpoint(params_path: str, opt_path: str | None, optimizer: Optimizer
     return st.tree, st
 
 
-def run_training(config, params, opt_state, *, kind, play_n_games_v3, make_replay, optimizer: Optimizer,
+def run_training(config, params, opt_state, *, play_n_games_v3, make_replay, optimizer: Optimizer,
                  init_params, input_shape, schedule, switch_guard, checkpoint_names, log=print):
     """The body of test_training (train_with_reward.py:168-309 / train_stochastic.py:201-355)."""
     seed = config["seed"]
