@@ -14,6 +14,8 @@
                                 MCTS agent (MADN/deterministic_madn.py:481-589: muzero_policy over the real
                                 environment with random-rollout leaf values), mcts.env_muzero_policy on the seat's
                                 gathered sub-batch with the evaluation's S / D, temperature 0 and no root noise.
+  'stochastic_mcts_agent'       the same for classic MADN (classic only): the reference's sketch with chance nodes for
+                                the die (MADN/classic_madn.py:543-714), stochastic.env_stochastic_muzero_policy.
   policy_action                 the random agent (770-775) and the rule-based agent (777-864) as one device
                                 kernel (muz_detmadn_policy_action), sampling by Gumbel-max on the counter RNG.
 
@@ -53,6 +55,12 @@ MCTS_AGENT = "mcts_agent"
 MCTS_ROLLOUT_STEPS = 300
 _NO_ENV_MODEL = ("no environment-model search kernel exists for this game (mcts.env_muzero_policy is det-MADN's); use "
                  "'random_agent', 'rule_based_agent' where the game has one, or a MuZero agent")
+# classic MADN's network-free MCTS seat (stochastic.env_stochastic_muzero_policy: the same construction with chance
+# nodes for the die; rollout cap of MADN/classic_madn.py's rollout, also 300)
+STOCHASTIC_MCTS_AGENT = "stochastic_mcts_agent"
+_NO_CHANCE_MODEL = ("the environment-model search with chance nodes (stochastic.env_stochastic_muzero_policy) is classic "
+                    "MADN's: det-MADN has no die (its seat is 'mcts_agent'), and DOG's hidden hands have no "
+                    "environment-model search kernel")
 
 # classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
 # defaults: no dice rethrow)
@@ -273,6 +281,7 @@ class _Game:
     instantiated).  ``env`` is the game's environment module, ``RULES`` its evaluation rules; ``search`` returns the
     actions of a gathered sub-batch, ``scripted`` those of the whole batch."""
     REFUSED = {MCTS_AGENT: _NO_ENV_MODEL}      # named agents the game cannot play -> why
+    ENV_SEAT = None                            # the name of the game's environment-search seat, if it has one
 
     @classmethod
     def reset(cls, n, sp, seed, device, r):
@@ -296,8 +305,10 @@ class _Game:
 
 class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
-    REFUSED = {}
+    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL}
+    ENV_SEAT = MCTS_AGENT
     workspace = staticmethod(M.SearchWorkspace)
+    env_workspace = staticmethod(M.EnvSearchWorkspace)
     scripted = staticmethod(policy_action)
 
     @staticmethod
@@ -330,7 +341,9 @@ class _Classic(_Game):
     """play_eval_loop_jitted's body_fn (evaluate_agent_stochastic.py:754-900): throw_die (its dice_probabilities,
     soft lock aware) before the agents move."""
     env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
+    ENV_SEAT = STOCHASTIC_MCTS_AGENT
     scripted = staticmethod(classic_policy_action)
+    env_workspace = staticmethod(ST.ClassicEnvSearchWorkspace)
 
     @staticmethod
     def pre_turn(env, gen):
@@ -358,6 +371,14 @@ class _Classic(_Game):
         return ST.stochastic_muzero_mcts(net, CL.encode_board(sub), bits, S, D, temperature, seed=seed, turn=turn,
                                          game_id=gid, workspace=ws)[0]
 
+    @staticmethod
+    def env_search(sub, gid, S, D, temperature, seed, turn, mws, rollout_steps=MCTS_ROLLOUT_STEPS):
+        """The 'stochastic_mcts_agent' seat: stochastic_muzero_policy over the real environment (the die of the turn
+        is thrown: pre_turn), no root noise, keyed by the games' ids."""
+        out, _ = ST.env_stochastic_muzero_policy(sub, S, D, temperature, rollout_steps=rollout_steps, seed=seed,
+                                                 turn=turn, game_id=gid, workspace=mws)
+        return out.action
+
 
 class _Dog(_Game):
     """Every game steps in its own lane each turn (a lane that does not move, a finished game's included, applies
@@ -367,7 +388,7 @@ class _Dog(_Game):
     # 806-action DOG mask cannot run, so the reference has no DOG rule-based agent to restate
     REFUSED = {"rule_based_agent": "MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to "
                                    "(4, 6) and cannot run; use 'random_agent' or a MuZero agent",
-               MCTS_AGENT: _NO_ENV_MODEL}
+               MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL}
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
 
@@ -411,16 +432,18 @@ def _seat(game, a, i, seed, device):
     if isinstance(a, str):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
-        if a not in ("rule_based_agent", "random_agent", MCTS_AGENT):
+        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
 
 
-def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None) -> bool:
+def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None,
+          rollout_steps=MCTS_ROLLOUT_STEPS) -> bool:
     """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
-    sub-batch of a seat (a network's, or the 'mcts_agent' seat's over the environment), or a scripted agent's launch
-    over the batch -- then the game's advance.  False, and nothing played, once every game is finished."""
+    sub-batch of a seat (a network's, or the game's environment-search seat's over the environment), or a scripted
+    agent's launch over the batch -- then the game's advance.  False, and nothing played, once every game is
+    finished."""
     active = env.done == 0
     game.pre_turn(env, gen)
     if not bool(active.any()):
@@ -433,9 +456,9 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
         sel = mover & (cp == s)
         if not bool(sel.any()):
             continue
-        if a == MCTS_AGENT:
+        if isinstance(a, str) and a == game.ENV_SEAT:
             idx = sel.nonzero().flatten()
-            act[idx] = game.env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws)
+            act[idx] = game.env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws, rollout_steps)
         elif isinstance(a, str):
             act = torch.where(sel, game.scripted(env, legal, a, seed, turn, rule_agent, gid), act)
         else:
@@ -450,7 +473,10 @@ def _workspace(game, seats, n, S, device):
 
 
 def _mcts_workspace(game, seats, n, S, device):
-    return M.EnvSearchWorkspace(n, S, device) if any(isinstance(x, str) and x == MCTS_AGENT for x in seats) else None
+    """The workspace of the game's environment-search seat, when one of the seats is that agent."""
+    if game.ENV_SEAT is None or not any(isinstance(x, str) and x == game.ENV_SEAT for x in seats):
+        return None
+    return game.env_workspace(n, S, device)
 
 
 def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_turns, rule_agent, device, skw,
@@ -513,8 +539,9 @@ def evaluate_agent_parallel_classic(agents, batch_size: int = 150, num_simulatio
                                     device="cuda") -> dict:
     """evaluate_agent_parallel (evaluate_agent_stochastic.py:253-315) with play_n_games_for_eval_jitted /
     play_eval_loop_jitted (717-936): `agents` = the four seats, each a DeviceClassicNet / Flax params (Stochastic
-    MuZero, temperature 0, S 75, D 50), None (randomly initialised params), 'rule_based_agent' or 'random_agent';
-    4 x batch_size games, block i started by player i; the die thrown every turn; at most 2000 turns.  Returns
+    MuZero, temperature 0, S 75, D 50), None (randomly initialised params), 'rule_based_agent', 'random_agent' or
+    'stochastic_mcts_agent' (the network-free MCTS over the dice environment, stochastic.env_stochastic_muzero_policy
+    with S / D, temperature and no root noise); 4 x batch_size games, block i started by player i; the die thrown every turn; at most 2000 turns.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals."""
     return _four_seats(_Classic, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns,
                        rule_agent, device, {})
@@ -523,10 +550,12 @@ def evaluate_agent_parallel_classic(agents, batch_size: int = 150, num_simulatio
 @torch.no_grad()
 def play_vs_random_classic(agent, num_games: int, num_simulations: int = CLASSIC_SIMULATIONS,
                            max_depth: int = CLASSIC_DEPTH, seed: int = 42, max_turns: int = 2000,
-                           rules: dict | None = None, device="cuda") -> dict:
+                           rules: dict | None = None, device="cuda", *,
+                           rollout_steps: int = MCTS_ROLLOUT_STEPS) -> dict:
     """One batch of test_agent_vs_random (evaluate_agent_stochastic.py:387-476): the agent at seat 0 (+ seat 2, its
     partner, with teams) -- a Stochastic MuZero searching at temperature 0 (multiactor_step_with_random_agent_v2,
-    478-650), or 'rule_based_agent' / 'random_agent' -- the other seats random; a random starting player per game
+    478-650), 'rule_based_agent' / 'random_agent', or 'stochastic_mcts_agent' (the network-free MCTS with rollouts of
+    at most ``rollout_steps`` turns) -- the other seats random; a random starting player per game
     (env_reset's seed); wins counted at seat 0.  The die is thrown every turn as play_eval_loop_jitted does: the v2
     step as written never throws it, so its games keep env_reset's die 0, have no legal pin and end only at
     MAX_STEPS (oracle/classic_madn.py: valid_action of a fresh state with die 0 is all False)."""
@@ -543,8 +572,10 @@ def play_vs_random_classic(agent, num_games: int, num_simulations: int = CLASSIC
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     ws = _workspace(_Classic, seats, num_games, num_simulations, device)
+    mws = _mcts_workspace(_Classic, seats, num_games, num_simulations, device)
     for turn in range(max_turns):
-        if not _turn(_Classic, env, seats, gid, turn, seed, gen, num_simulations, max_depth, 0.0, None, ws, {}):
+        if not _turn(_Classic, env, seats, gid, turn, seed, gen, num_simulations, max_depth, 0.0, None, ws, {}, mws,
+                     rollout_steps):
             break
     w = winners(env, teams) & (env.done != 0)[:, None]
     prog = calculate_progress(env, bool(r.get("must_traverse_start", False)))

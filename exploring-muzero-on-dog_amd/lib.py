@@ -379,6 +379,10 @@ SIGNATURES = {
     "muz_detmadn_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzPuctCfg),
                                         ctypes.POINTER(MuzEnvMctsCfg), MuzDetSoA, vp, vp, vp, ctypes.c_int32, vp,
                                         ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
+    "muz_classic_mcts_tree_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(MuzStochCfg)]),
+    "muz_classic_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzStochCfg),
+                                        ctypes.POINTER(MuzEnvMctsCfg), MuzClassicSoA, vp, vp, vp, ctypes.c_int32, vp,
+                                        ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
     "muz_selfplay_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(MuzSearchCfg)]),
     "muz_detmadn_selfplay": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzNetW),
                                             ctypes.POINTER(MuzSearchCfg), MuzDetSoA, MuzTraj, ctypes.c_int32, vp,

@@ -162,6 +162,68 @@ def stochastic_muzero_policy(net: DeviceClassicNet, root_logits, root_value, roo
     return action, weights, value
 
 
+class ClassicEnvSearchWorkspace:
+    """Device workspace of env_stochastic_muzero_policy for B searches: the tree's own carve
+    (muz_classic_mcts_tree_bytes: children arrays and a 64-byte state row per node, no latent slots)."""
+
+    def __init__(self, batch: int, num_simulations: int, device="cuda"):
+        cfg = make_cfg(num_simulations, 1)
+        self.batch, self.S = batch, num_simulations
+        nbytes = _L.load().muz_classic_mcts_tree_bytes(batch, ctypes.byref(cfg))
+        if nbytes < 0:
+            raise _L.MuzError(f"env_stochastic_muzero_policy: num_simulations {num_simulations} is outside the "
+                              "kernel's limits")
+        self.tree = torch.empty((nbytes,), dtype=torch.uint8, device=device)
+
+    def fits(self, batch, S):
+        return batch <= self.batch and S <= self.S
+
+    def rollout_turns(self, batch: int) -> torch.Tensor:
+        """int32 [batch]: the rollout turns each game of the last search of ``batch`` games played."""
+        return self.tree[:4 * batch].view(torch.int32)
+
+
+def env_stochastic_muzero_policy(env, num_simulations, max_depth, temperature=0.0, *, rollout_steps=300, seed, turn,
+                                 game_id=None, workspace: ClassicEnvSearchWorkspace | None = None, summary=False,
+                                 dirichlet_fraction=0.0, dirichlet_alpha=0.3, pb_c_init=1.25, pb_c_base=19652.0,
+                                 dirichlet=None, gumbel=None):
+    """The network-free MCTS agent the reference sketches for classic MADN (MADN/classic_madn.py:543-714):
+    mctx.stochastic_muzero_policy whose model is the dice environment itself -- decision nodes with prior logits 100
+    legal + 200 winning, chance nodes with the environment's own die probabilities, random-rollout leaf values of at
+    most ``rollout_steps`` turns -- on the states of ``env`` (a classic.ClassicMADNState with its die thrown, read
+    only), one persistent kernel (csrc/classic_env_mcts.hip).  The semantics the reference leaves open are fixed in
+    include/muz.h (muz_classic_mcts); parity with the reference is unpinned.  No root noise by default (an evaluation
+    agent).  A game that is finished or has no legal pin for its die is not searched: action -1, weights 0, value 0.
+    Returns (PolicyOutput, root_value clipped to [-1, 1]), with ``summary`` also the root's visit_counts (int32
+    [B, 4]) and qvalues (fp32 [B, 4]; unvisited children 0)."""
+    from . import classic as _E
+    from .mcts import PolicyOutput
+    if not isinstance(env, _E.ClassicMADNState):
+        raise TypeError("env_stochastic_muzero_policy searches classic-MADN states (classic.ClassicMADNState): no "
+                        f"environment-model kernel with chance nodes exists for {type(env).__name__}")
+    lib = _L.load()
+    B = env.batch
+    dev = env.board.device
+    cfg = make_cfg(num_simulations, max_depth, temperature, seed, turn, dirichlet_fraction, dirichlet_alpha, pb_c_init,
+                   pb_c_base)
+    mcfg = _L.MuzEnvMctsCfg(int(rollout_steps))
+    if workspace is None or not workspace.fits(B, num_simulations):
+        workspace = ClassicEnvSearchWorkspace(B, num_simulations, dev)
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, A_CLASSIC), dtype=torch.float32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    visits = torch.empty((B, A_CLASSIC), dtype=torch.int32, device=dev) if summary else None
+    qvalues = torch.empty((B, A_CLASSIC), dtype=torch.float32, device=dev) if summary else None
+    dn = None if dirichlet is None else _f32(dirichlet.to(dev))
+    g = None if gumbel is None else _f32(gumbel.to(dev))
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).contiguous()
+    _L.check(lib.muz_classic_mcts(env.rules, ctypes.byref(cfg), mcfg, env.soa(), _L.ptr(dn), _L.ptr(g), _L.ptr(gid), B,
+                                  _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action), _L.ptr(weights),
+                                  _L.ptr(value), _L.ptr(visits), _L.ptr(qvalues), _L.stream_ptr()), "muz_classic_mcts")
+    out = (PolicyOutput(action, weights), value)
+    return out + (visits, qvalues) if summary else out
+
+
 def stochastic_muzero_mcts(net: DeviceClassicNet, observations, legal_bits, num_simulations, max_depth,
                            temperature, seed=0, turn=0, **kw):
     """Device-native form of run_stochastic_muzero_mcts: DeviceClassicNet, device observations, 4-bit legal

@@ -664,6 +664,51 @@ int muz_stochastic_search(const muz_classic_net_w* w, const muz_stoch_cfg* cfg, 
                           void* workspace, int64_t workspace_bytes, int32_t* action, float* action_weights,
                           float* root_value_out, void* stream);
 
+/* ---- network-free MCTS agent for classic MADN: stochastic_muzero_policy over the real environment ------------
+ * The reference's sketch of an MCTS whose model is the dice environment itself, with random-rollout leaf values
+ * (MADN/classic_madn.py:543-714 winning_action / policy_function / rollout / value_function / recurrent_chance_fn /
+ * recurrent_fn / root_fn, meant for mctx.stochastic_muzero_policy).  That path cannot run as written (winning_action
+ * builds its state without `key`), never changes the discount's sign between sides and gives every chance node uniform
+ * logits, so parity with it is UNPINNED; the definition is tests/_classic_env_mcts.py, which the kernel
+ * (csrc/classic_env_mcts.hip) equals bit for bit.  side(p) = p % 2 with teams, else p:
+ *   root        a state whose die is thrown; done, or without a legal pin for its die: not searched (action -1,
+ *               weights 0, value 0)
+ *   decision    mask valid_action (4 bits), prior logits 100 legal + 200 wins (wins: pin legal and env_step returns
+ *               reward 1), actions outside the mask excluded at every decision node; a non-root decision node that is
+ *               done or has no legal pin has exactly one action, pin 0, which applies no_step
+ *   -> chance   afterstate = env_step / no_step; edge reward 0, discount 1; the chance node keeps (reward, discount):
+ *               env_step's reward (0 for no_step); 0 if done, +1 if side(next to move) == side(mover), else -1
+ *   chance      child priors dice_probabilities(afterstate) as they are (1/6, or the 76/216 and 91/216 tables of a
+ *               soft-locked player under enable_dice_rethrow); selection argmax p[c] / (n[c] + 1); value a rollout from
+ *               the afterstate seen from the side that moved -- of a finished afterstate the kept reward (the +1 the
+ *               mover's side has just won, which a zero-turn rollout returns and the outgoing edges back up, so that
+ *               the q-value of a winning pin is exactly 1)
+ *   -> decision state = afterstate with die c + 1; edge reward / discount the chance node's; value 0 if done, else a
+ *               rollout seen from the side to move
+ *   rollout     at most rollout_steps turns: throw the die with choice(dice_probabilities, u0) (the first turn of a
+ *               decision node's rollout keeps the node's die), then no_step without a legal pin, else a uniform pick
+ *               among wins if any, else among legal: the k-th set bit, k = min(floor(u1 count), count - 1); u0 / u1
+ *               the counter RNG of (seed, game, turn, node -- 0 the root, i + 1 simulation i --, 2 t / 2 t + 1), a
+ *               stream of its own; +1 if the viewing side has won, -1 if another side has, 0 at the cap
+ *   search      muz_stochastic_search's (PUCT with qtransform_by_parent_and_siblings, the 1e-7 tie-break), muz_stoch_cfg
+ *               whole (Dirichlet fraction 0 for evaluation); weights = root visit fractions, root value clipped. */
+/* Bytes of the tree's own workspace: per game an int32 count of rollout turns, then per node six 16-wide children
+ * arrays and a 64-byte state row.  -1 for a null cfg, n < 0 or S / D outside the limits.  (Not a *_workspace_bytes
+ * name, as muz_detmadn_mcts_tree_bytes; pinned in tests/test_classic_env_mcts_host.py.) */
+int64_t muz_classic_mcts_tree_bytes(int32_t n, const muz_stoch_cfg* cfg /*host*/);
+/* The contract of muz_detmadn_mcts: state is read only (its die set); dirichlet / gumbel [n][4] / game_id as
+ * muz_stochastic_search.  Outputs: action [n], action_weights [n][4], root_value [n] clipped to [-1, 1], and the
+ * root's visit_counts [n][4] / qvalues [n][4] (each nullable; unvisited children report 0).  After the call the first
+ * n int32 of the workspace hold each game's number of rollout turns.  MUZ_E_UNSUPPORTED: S or D outside the limits,
+ * rollout_steps outside 0..1000, a Dirichlet fraction outside [0, 1], alpha or pb_c_base <= 0, temperature < 0 (or a
+ * NaN), rules the classic entry points refuse.  MUZ_E_INVALID: a null pointer, a workspace shorter than
+ * muz_classic_mcts_tree_bytes or not 16-byte aligned.  Checked before any launch; n == 0 returns MUZ_OK. */
+int muz_classic_mcts(const muz_rules* rules /*host*/, const muz_stoch_cfg* cfg /*host*/,
+                     const muz_env_mcts_cfg* mcfg /*host*/, muz_classic_soa state, const float* dirichlet,
+                     const float* gumbel, const int32_t* game_id, int32_t n, void* workspace, int64_t workspace_bytes,
+                     int32_t* action, float* action_weights, float* root_value, int32_t* visit_counts,
+                     float* qvalues, void* stream);
+
 /* Diagnostic readout of the root Dirichlet noise that muz_stochastic_search (num_actions 4) and muz_puct_search
  * (num_actions 24) draw on the device when their `dirichlet` argument is NULL, through the helper both kernels call
  * (csrc/rng.hpp root_noise_log_gamma) and each search's own row normalisation.  Its own contract: for row r < n,
