@@ -42,7 +42,7 @@ struct DogG {   // one game in LDS
   float key[kMaxPool];
   int8_t pool[kMaxPool];
   int8_t shuffled[kMaxPool];
-  unsigned long long wb[7];     // base validity bits by checking slot (env_dog.hip: dog_check_of)
+  unsigned long long wb[7];     // base validity bits by checking slot (dog_env.hpp: dog_check_of)
   unsigned long long wj[7], wr[7];   // k_dog_play: legal joker / real-card copies by checking slot
   int need_deal;
 };

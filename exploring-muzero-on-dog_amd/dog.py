@@ -14,9 +14,13 @@ Reference entry points mirrored (file:line in the reference):
 The shuffle keys of a deal come from the engine's counter RNG (include/muz.h, DOG section) instead of
 jax threefry; ``oracle/dog.py:engine_shuffle_keys`` restates them for the parity tests.  The
 reference's ``encode_board`` is a stub (dog.py:1264-1272), so there is no DOG observation here.
+
+``rollout_policy`` is the network-free rollout agent (csrc/dog_rollout.hip): the reference has no DOG agent that
+runs, so it is this engine's own and parity-unpinned; ``tests/_dog_rollout.py`` defines it.
 """
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 
 import numpy as np
@@ -222,6 +226,49 @@ def random_action(mask: torch.Tensor, uniform: torch.Tensor | None = None, seed=
     _call("muz_dog_random_action", _L.ptr(mask), _L.ptr(u), ctypes_u64(seed), int(turn), _L.ptr(out), B,
           _L.stream_ptr())
     return out
+
+
+# ---- the network-free rollout agent (csrc/dog_rollout.hip; include/muz.h, DOG rollout agent) -------------------------
+class RolloutWorkspace:
+    """The device workspace of ``rollout_policy`` for up to ``n`` games (muz_dog_rollout_bytes)."""
+
+    def __init__(self, n: int, device="cuda"):
+        self.n = int(n)
+        self.buf = torch.empty((int(_L.load().muz_dog_rollout_bytes(self.n)),), dtype=torch.uint8, device=device)
+
+
+def rollout_policy(env, rollouts: int = 4, *, max_phases: int = 10, rollout_steps: int = 300, determinize: bool = True,
+                   seed: int, turn: int, game_id: torch.Tensor | None = None,
+                   workspace: RolloutWorkspace | None = None, summary: bool = False):
+    """The rollout agent's action for every game of ``env`` (int32 [B]; -1 for a finished game or one without a legal
+    action): every legal action is tried on copies of the game whose hidden cards are re-drawn (``determinize``), each
+    copy is played out with the random policy for at most ``rollout_steps`` turns, and the actions are thinned by
+    sequential halving on their win counts, ``rollouts`` playouts per action and phase, at most ``max_phases`` phases
+    (muz_dog_rollout_search; the semantics are in include/muz.h, the definition is tests/_dog_rollout.py -- the
+    reference has no DOG agent, parity is unpinned).  ``env`` is not changed.  The playouts are keyed by ``seed``,
+    ``turn`` and ``game_id`` (default: the position in the batch), so both are required.  With ``summary`` returns
+    (action, value float32 [B], visits int32 [B, 806], wins int32 [B, 806], rollout_turns int32 [B])."""
+    if not isinstance(env, DOGState):
+        raise TypeError(f"rollout_policy searches a DOG state (dog.DOGState), not {type(env).__name__}")
+    B, dev = env.batch, env.board.device
+    if workspace is None:
+        workspace = RolloutWorkspace(B, dev)
+    if workspace.n < B:
+        raise ValueError(f"the workspace holds {workspace.n} games, the state {B}")
+    cfg = _L.MuzDogRolloutCfg(int(rollouts), int(max_phases), int(rollout_steps), int(bool(determinize)),
+                              ctypes_u64(seed), int(turn))
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    visits = wins = turns = None
+    if summary:
+        visits = torch.empty((B, ACTIONS), dtype=torch.int32, device=dev)
+        wins = torch.empty((B, ACTIONS), dtype=torch.int32, device=dev)
+        turns = torch.empty((B,), dtype=torch.int32, device=dev)
+    _call("muz_dog_rollout_search", env.rules, ctypes.byref(cfg), env.soa(), _L.ptr(gid), _L.ptr(action), _L.ptr(value),
+          _L.ptr(visits), _L.ptr(wins), _L.ptr(turns), B, _L.ptr(workspace.buf), _L.nbytes(workspace.buf),
+          _L.stream_ptr())
+    return (action, value, visits, wins, turns) if summary else action
 
 
 # ---- action <-> move helpers (dog.py:1133-1262), host side ---------------------------------------------

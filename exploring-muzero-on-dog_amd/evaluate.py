@@ -16,6 +16,9 @@
                                 gathered sub-batch with the evaluation's S / D, temperature 0 and no root noise.
   'stochastic_mcts_agent'       the same for classic MADN (classic only): the reference's sketch with chance nodes for
                                 the die (MADN/classic_madn.py:543-714), stochastic.env_stochastic_muzero_policy.
+  'rollout_agent'               DOG's network-free seat (DOG only): a root-level Monte-Carlo search over the real
+                                environment with re-drawn hidden cards, dog.rollout_policy (the reference has no DOG
+                                agent that runs; parity unpinned).
   policy_action                 the random agent (770-775) and the rule-based agent (777-864) as one device
                                 kernel (muz_detmadn_policy_action), sampling by Gumbel-max on the counter RNG.
 
@@ -54,13 +57,20 @@ RULES = dict(E.SELFPLAY_RULES)
 MCTS_AGENT = "mcts_agent"
 MCTS_ROLLOUT_STEPS = 300
 _NO_ENV_MODEL = ("no environment-model search kernel exists for this game (mcts.env_muzero_policy is det-MADN's); use "
-                 "'random_agent', 'rule_based_agent' where the game has one, or a MuZero agent")
+                 "'random_agent', 'rule_based_agent' where the game has one, a MuZero agent, or for DOG 'rollout_agent'")
 # classic MADN's network-free MCTS seat (stochastic.env_stochastic_muzero_policy: the same construction with chance
 # nodes for the die; rollout cap of MADN/classic_madn.py's rollout, also 300)
 STOCHASTIC_MCTS_AGENT = "stochastic_mcts_agent"
 _NO_CHANCE_MODEL = ("the environment-model search with chance nodes (stochastic.env_stochastic_muzero_policy) is classic "
                     "MADN's: det-MADN has no die (its seat is 'mcts_agent'), and DOG's hidden hands have no "
-                    "environment-model search kernel")
+                    "environment-model search kernel (its network-free seat is 'rollout_agent')")
+# DOG's network-free seat (dog.rollout_policy: root-level Monte-Carlo with re-drawn hidden cards and sequential halving)
+ROLLOUT_AGENT = "rollout_agent"
+ROLLOUT_DEFAULTS = dict(rollouts=4, rollout_steps=MCTS_ROLLOUT_STEPS, determinize=True)
+_NO_ROLLOUT_DET = ("the rollout agent (dog.rollout_policy) is DOG's: det-MADN's network-free seat is 'mcts_agent'; its "
+                   "other named seats are 'rule_based_agent' and 'random_agent'")
+_NO_ROLLOUT_CLASSIC = ("the rollout agent (dog.rollout_policy) is DOG's: classic MADN's network-free seat is "
+                       "'stochastic_mcts_agent'; its other named seats are 'rule_based_agent' and 'random_agent'")
 
 # classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
 # defaults: no dice rethrow)
@@ -282,6 +292,7 @@ class _Game:
     actions of a gathered sub-batch, ``scripted`` those of the whole batch."""
     REFUSED = {MCTS_AGENT: _NO_ENV_MODEL}      # named agents the game cannot play -> why
     ENV_SEAT = None                            # the name of the game's environment-search seat, if it has one
+    ROLLOUT_SEAT = None                        # the name of the game's root-level rollout seat, if it has one
 
     @classmethod
     def reset(cls, n, sp, seed, device, r):
@@ -305,7 +316,7 @@ class _Game:
 
 class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
-    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL}
+    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET}
     ENV_SEAT = MCTS_AGENT
     workspace = staticmethod(M.SearchWorkspace)
     env_workspace = staticmethod(M.EnvSearchWorkspace)
@@ -341,6 +352,7 @@ class _Classic(_Game):
     """play_eval_loop_jitted's body_fn (evaluate_agent_stochastic.py:754-900): throw_die (its dice_probabilities,
     soft lock aware) before the agents move."""
     env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
+    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC}
     ENV_SEAT = STOCHASTIC_MCTS_AGENT
     scripted = staticmethod(classic_policy_action)
     env_workspace = staticmethod(ST.ClassicEnvSearchWorkspace)
@@ -389,8 +401,15 @@ class _Dog(_Game):
     REFUSED = {"rule_based_agent": "MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to "
                                    "(4, 6) and cannot run; use 'random_agent' or a MuZero agent",
                MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL}
+    ROLLOUT_SEAT = ROLLOUT_AGENT
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
+    rollout_workspace = staticmethod(DOG.RolloutWorkspace)
+
+    @staticmethod
+    def rollout_search(sub, gid, seed, turn, rws, rollout):
+        """The 'rollout_agent' seat: dog.rollout_policy on the seat's gathered games, keyed by the games' ids."""
+        return DOG.rollout_policy(sub, seed=seed, turn=turn, game_id=gid, workspace=rws, **rollout)
 
     @staticmethod
     def reset(n, sp, seed, device, r):   # block sp's deals are keyed by seed + sp
@@ -432,17 +451,18 @@ def _seat(game, a, i, seed, device):
     if isinstance(a, str):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
-        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT):
+        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.ROLLOUT_SEAT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
 
 
 def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None,
-          rollout_steps=MCTS_ROLLOUT_STEPS) -> bool:
+          rollout_steps=MCTS_ROLLOUT_STEPS, rws=None, rollout=None) -> bool:
     """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
-    sub-batch of a seat (a network's, or the game's environment-search seat's over the environment), or a scripted
-    agent's launch over the batch -- then the game's advance.  False, and nothing played, once every game is
+    sub-batch of a seat (a network's, the game's environment-search seat's over the environment, or the game's
+    rollout seat's with the keywords ``rollout``), or a scripted agent's launch over the batch -- then the game's
+    advance.  False, and nothing played, once every game is
     finished."""
     active = env.done == 0
     game.pre_turn(env, gen)
@@ -459,6 +479,10 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
         if isinstance(a, str) and a == game.ENV_SEAT:
             idx = sel.nonzero().flatten()
             act[idx] = game.env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws, rollout_steps)
+        elif isinstance(a, str) and a == game.ROLLOUT_SEAT:
+            idx = sel.nonzero().flatten()
+            act[idx] = game.rollout_search(env.take(idx), gid[idx], seed, turn, rws,
+                                           ROLLOUT_DEFAULTS if rollout is None else rollout)
         elif isinstance(a, str):
             act = torch.where(sel, game.scripted(env, legal, a, seed, turn, rule_agent, gid), act)
         else:
@@ -479,8 +503,15 @@ def _mcts_workspace(game, seats, n, S, device):
     return game.env_workspace(n, S, device)
 
 
+def _rollout_workspace(game, seats, n, device):
+    """The workspace of the game's rollout seat, when one of the seats is that agent."""
+    if game.ROLLOUT_SEAT is None or not any(isinstance(x, str) and x == game.ROLLOUT_SEAT for x in seats):
+        return None
+    return game.rollout_workspace(n, device)
+
+
 def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_turns, rule_agent, device, skw,
-                report_turns=False) -> dict:
+                report_turns=False, rollout=None) -> dict:
     """4 x batch_size games of ``game``, block i started by player i, played to the end or ``max_turns``; the result
     tables, with ``report_turns`` also the number of turns the loop ran."""
     r = dict(game.RULES if rules is None else rules)
@@ -494,10 +525,12 @@ def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_tu
     gen.manual_seed(seed)
     ws = _workspace(game, seats, n, S, device)
     mws = _mcts_workspace(game, seats, n, S, device)
+    rws = _rollout_workspace(game, seats, n, device)
     turns = 0
     for turn in range(max_turns):
         turns = turn + 1
-        if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws):
+        if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws, rws=rws,
+                     rollout=rollout):
             break
     return _tables(env, r, batch_size, **({"turns": turns} if report_turns else {}))
 
@@ -609,14 +642,18 @@ def compare_agents_statistically_classic(agent1, agent2, num_games: int = 1000, 
 @torch.no_grad()
 def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: int = DOG_SIMULATIONS,
                                 max_depth: int = DOG_DEPTH, temperature: float = DOG_TEMPERATURE, seed: int = 0,
-                                rules: dict | None = None, max_turns: int = 2000, device="cuda") -> dict:
+                                rules: dict | None = None, max_turns: int = 2000, device="cuda", *, rollouts: int = 4,
+                                rollout_steps: int = MCTS_ROLLOUT_STEPS, determinize: bool = True) -> dict:
     """evaluate_agent_parallel (MuZero_DOG/evaluate_agent.py:255-313) with play_n_games_for_eval_jitted /
     play_eval_loop_jitted (315-527): `agents` = the four seats, each the DOG slice's MuZero (a DeviceDogNet or its
-    flat params; None = randomly initialised params; run_muzero_mcts at A = 806, S 100, D 50, temperature 0.2) or
-    'random_agent' (do_random: a uniform legal action); 4 x batch_size games, block i started by player i, at most
+    flat params; None = randomly initialised params; run_muzero_mcts at A = 806, S 100, D 50, temperature 0.2),
+    'random_agent' (do_random: a uniform legal action) or 'rollout_agent' (the network-free root-level Monte-Carlo
+    search dog.rollout_policy with ``rollouts`` playouts per action and phase of at most ``rollout_steps`` turns, the
+    hidden cards re-drawn when ``determinize``; keyed by seed, turn and the game's index); 4 x batch_size games, block i started by player i, at most
     2000 turns; a game without a legal action applies no_step.  Every game steps in its own lane each turn (a finished
     game's lane applies no_step, which leaves its pins alone), so a game's deals are keyed by its own index.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals.
     Win-rate parity is unpinned: the reference's DOG networks and inference functions are `pass`."""
     return _four_seats(_Dog, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns, None,
-                       device, {}, report_turns=True)
+                       device, {}, report_turns=True,
+                       rollout=dict(rollouts=rollouts, rollout_steps=rollout_steps, determinize=determinize))

@@ -289,6 +289,62 @@ int muz_dog_step_move(const muz_rules* rules, muz_dog_soa state, const int32_t* 
 int muz_dog_random_action(const uint32_t* mask, const float* uniform, uint64_t seed, int32_t turn, int32_t* action,
                           int32_t n, void* stream);
 
+/* ---- DOG rollout agent: a network-free root-level Monte-Carlo search (csrc/dog_rollout.hip) -----------------------
+ * The reference has no DOG agent that runs (its rule-based one reshapes the 806-action mask to (4, 6)), so parity with
+ * it is UNPINNED; the definition is tests/_dog_rollout.py, which the kernels equal bit for bit (every result is an
+ * integer sum).  For one root game with its game_id, cfg.turn and cfg.seed:
+ *   m = the current player, m' = dog_sub(m) (the partner, when m is a finished team player); the OBSERVERS are
+ *   {m, m'}; the SIDE is m & 1 with teams, else the seat m; C0 = the bits of muz_dog_legal's mask, ascending.
+ *   A game that is done, or whose C0 is empty: action -1, all visits 0, value 0.  |C0| == 1: that action, no rollout,
+ *   visits 0, value 0.
+ *   Phases p = 0, 1, .. until max_phases have run or one candidate is left: every candidate a of Cp gets R = rollouts
+ *   rollouts j = p R .. p R + R - 1 (so the candidates of a phase have equal visits); the candidates are ranked by
+ *   wins[a] (int32 sum of outcomes) descending, ties by the smaller action; C(p+1) = the best ceil(|Cp| / 2).  The
+ *   action is the best candidate of the last ranked set, value = float32(wins) / float32(visits) of it (one IEEE
+ *   division).
+ *   Rollout (a, j): copy the root; with determinize != 0 re-draw the hidden cards (below); apply a with env_step (and
+ *   the deal it asks for); if that ends the game the outcome is decided, else play muz_dog_random_turn turns (no_step
+ *   when nothing is legal) t = 0, 1, .. until the game is done or rollout_steps turns are played.  Outcome: +1 when
+ *   dog_winners of the final board holds the side, -1 when it is non-empty and does not, 0 otherwise (the cap).
+ *   rollout_turns counts the random turns played (the root action is not one).
+ *   Streams: rollout j has the 64-bit seed
+ *     rseed = mix64(seed ^ 0xD06B0110A7 ^ mix64(game_id << 32 | turn) ^ (j+1) * 0xC2B2AE3D27D4EB4F),
+ *   and draws the engine's own streams under it: shuffle keys of a deal as above with (rseed, game_id, the copy's deal
+ *   counter), the uniform of random turn t as muz_dog_random_action's with (rseed, game_id, t); the determinization's
+ *   i-th draw is U24(mix64(rseed ^ 0xD06DE7E5 ^ (i+1) * 0x9FB21C651E98DF25)).  Nothing is keyed by the action a (the
+ *   candidates of a phase share their random numbers) or by the game's position in the batch.
+ *   Determinization: the hidden multiset H (counts over the 14 cards) = deck + the hands of every seat that is not an
+ *   observer + one card for every such seat q with 0 <= swap_choices[q] < 14 (in the swap phase a chosen card has left
+ *   the hand and is handed over later).  For those seats q ascending: draw as many cards as q's hand holds, then q's
+ *   swap choice if it had one; each draw takes the floor(u |H|)-th card of H in card order, without replacement.  What
+ *   is left of H becomes the deck.  The observers' hands and swap choices, board, pins, phase, hand sizes and the deal
+ *   counter stay.  (The mover also knows the card it gave its partner in the swap phase; that knowledge is ignored:
+ *   the partner's hand is re-drawn like any hidden hand.) */
+typedef struct muz_dog_rollout_cfg {
+  int32_t rollouts;      /* R, 1..64 */
+  int32_t max_phases;    /* 1..10 */
+  int32_t rollout_steps; /* 1..1000 */
+  int32_t determinize;
+  uint64_t seed;
+  int32_t turn;
+} muz_dog_rollout_cfg;
+/* Workspace of muz_dog_rollout_search for n games (-1 for n < 0): wins, visits and candidate lists [n][806] int32,
+ * then candidate counts [n], rollout turns [n] and item offsets [n + 1], each block rounded up to 256 bytes.  (Not a
+ * *_workspace_bytes name: those are the searches' trees; pinned in tests/test_dog_rollout_host.py.) */
+int64_t muz_dog_rollout_bytes(int32_t n);
+/* The search of every game of `state` (read only) on `stream`, without a host synchronisation: one candidate-list
+ * launch, then per phase a plan, a rollout and a ranking launch.  game_id null: 0..n-1.  visits / wins [n][806] and
+ * rollout_turns [n] may be null.  All checks come before any launch: MUZ_E_INVALID for a null rules / cfg / action /
+ * value / workspace / state field, a workspace shorter than muz_dog_rollout_bytes(n) or not 16-byte aligned, a cfg out
+ * of range, n < 0, n > state.stride or n * 806 * rollouts > 2^31 - 1 - 2048 (the items of a phase are indexed in int32: at most
+ * 41,630 games at 64 rollouts, 666,092 at the default 4); MUZ_E_UNSUPPORTED for the rules the muz_dog_* entry points refuse; n == 0 is
+ * MUZ_OK with nothing launched. */
+int muz_dog_rollout_search(const muz_rules* rules /*host*/, const muz_dog_rollout_cfg* cfg /*host*/,
+                           muz_dog_soa state /* read only */, const int32_t* game_id /* null: 0..n-1 */,
+                           int32_t* action, float* value, int32_t* visits /* [n][806], nullable */,
+                           int32_t* wins /* [n][806], nullable */, uint32_t* rollout_turns /* [n], nullable */,
+                           int32_t n, void* ws, int64_t ws_bytes, void* stream);
+
 /* ---- MuZero networks (MuZero_det_MADN/muzero_deterministic_madn.py) --------------------------
  * Dense layers used by the MFMA kernels take their kernel W[K][N] PACKED for
  * v_mfma_f32_16x16x4_f32 B-fragments: [group][K/16][lane 64][tile NT][j 4] (group = wave, see muz_tile_waves) with
