@@ -76,35 +76,7 @@ struct GumbelTree : TreeWs {
   }
 };
 
-// qtransform_completed_by_mix_value's prior_probs of this lane's child, softmax(prior logits) clamped at the smallest
-// normal float; pm: the row's largest prior logit.
-__device__ __forceinline__ float prior_probs(float prior, bool ok, float& pm) {
-#pragma clang fp contract(off)
-  pm = row_max(ok ? prior : -INFINITY);
-  const float e = ok ? exp_cr(prior - pm) : 0.f;
-  const float es = row_sum24(e);
-  return fmaxf(kTinyF, e / es);
-}
-
-// qtransform_completed_by_mix_value (value_scale, maxvisit_init, rescale, mixed value, eps 1e-8); pp: prior_probs of
-// the node's children.
-__device__ __forceinline__ float completed_q(const Kid& k, float pp, float raw, const SearchArgs& sa, int& sumv) {
-#pragma clang fp contract(off)
-  const float q = k.reward + k.disc * k.value;
-  const bool vis = k.ok && k.visits > 0;
-  const int sv = row_isum(k.ok ? k.visits : 0);
-  const int mv = row_imax(k.ok ? k.visits : 0);
-  const float sp = row_sum24(vis ? pp : 0.f);
-  const float wq = row_sum24(vis ? pp * q / sp : 0.f);
-  const float mixed = (raw + (float)sv * wq) / (float)(sv + 1);
-  float cq = vis ? q : mixed;
-  const float lo = row_min(k.ok ? cq : INFINITY);
-  const float hi = row_max(k.ok ? cq : -INFINITY);
-  const float den = fmaxf(hi - lo, 1e-8f);
-  const float scale = (sa.maxvisit_init + (float)mv) * sa.value_scale;
-  sumv = sv;
-  return scale * ((cq - lo) / den);
-}
+// (prior_probs and completed_q, qtransform_completed_by_mix_value's two halves: tree.hpp, shared with k_env_gumbel)
 
 template <int PARTS>
 __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(

@@ -4,6 +4,8 @@
 // loop around the kernel's score), commit_expansion and commit_backup -- and differ in their root, score and tail.
 // k_env_mcts (env_mcts.hip) is k_puct_search's body and score (value_score, row_softmax24 below) around an expansion
 // that steps the environment instead of the networks, on a carve of its own.
+// k_env_gumbel (env_gumbel.hip) is that expansion (env_model.hpp) under k_gumbel_search's scores (prior_probs,
+// completed_q below).
 // k_stochastic_search shares the tree layout and row_argmax and keeps its own walk, expansion and one-lane backup
 // written out (on the shared body it was 0.3 % slower per classic self-play step, and needed 247 VGPRs with
 // commit_backup: profiles/search_body_refactor.log); k_dog_search (806 children per node, its own walk and backup)
@@ -114,6 +116,36 @@ __device__ __forceinline__ float row_softmax24(float x, bool ok) {
   const float m = row_max(ok ? x : -INFINITY);
   const float e = ok ? exp_cr(x - m) : 0.f;
   return e / row_sum24(e);
+}
+
+// qtransform_completed_by_mix_value's prior_probs of this lane's child, softmax(prior logits) clamped at the smallest
+// normal float; pm: the row's largest prior logit.  (k_gumbel_search, k_env_gumbel)
+__device__ __forceinline__ float prior_probs(float prior, bool ok, float& pm) {
+#pragma clang fp contract(off)
+  pm = row_max(ok ? prior : -INFINITY);
+  const float e = ok ? exp_cr(prior - pm) : 0.f;
+  const float es = row_sum24(e);
+  return fmaxf(kTinyF, e / es);
+}
+
+// qtransform_completed_by_mix_value (value_scale, maxvisit_init, rescale, mixed value, eps 1e-8); pp: prior_probs of
+// the node's children.
+__device__ __forceinline__ float completed_q(const Kid& k, float pp, float raw, const SearchArgs& sa, int& sumv) {
+#pragma clang fp contract(off)
+  const float q = k.reward + k.disc * k.value;
+  const bool vis = k.ok && k.visits > 0;
+  const int sv = row_isum(k.ok ? k.visits : 0);
+  const int mv = row_imax(k.ok ? k.visits : 0);
+  const float sp = row_sum24(vis ? pp : 0.f);
+  const float wq = row_sum24(vis ? pp * q / sp : 0.f);
+  const float mixed = (raw + (float)sv * wq) / (float)(sv + 1);
+  float cq = vis ? q : mixed;
+  const float lo = row_min(k.ok ? cq : INFINITY);
+  const float hi = row_max(k.ok ? cq : -INFINITY);
+  const float den = fmaxf(hi - lo, 1e-8f);
+  const float scale = (sa.maxvisit_init + (float)mv) * sa.value_scale;
+  sumv = sv;
+  return scale * ((cq - lo) / den);
 }
 
 // seq_halving.get_sequence_of_considered_visits(m, S)[idx] without the table.

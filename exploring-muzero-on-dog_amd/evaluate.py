@@ -14,6 +14,9 @@
                                 MCTS agent (MADN/deterministic_madn.py:481-589: muzero_policy over the real
                                 environment with random-rollout leaf values), mcts.env_muzero_policy on the seat's
                                 gathered sub-batch with the evaluation's S / D, temperature 0 and no root noise.
+  'gumbel_mcts_agent'           the same seat under the Gumbel policy (det-MADN only): the call the reference drives
+                                (MADN/simulate_deterministicMADN.py:12-35 run_gumbel), mcts.env_gumbel_muzero_policy
+                                with the evaluation's S / D and temperature as its Gumbel scale.
   'stochastic_mcts_agent'       the same for classic MADN (classic only): the reference's sketch with chance nodes for
                                 the die (MADN/classic_madn.py:543-714), stochastic.env_stochastic_muzero_policy.
   'rollout_agent'               DOG's network-free seat (DOG only): a root-level Monte-Carlo search over the real
@@ -58,6 +61,13 @@ MCTS_AGENT = "mcts_agent"
 MCTS_ROLLOUT_STEPS = 300
 _NO_ENV_MODEL = ("no environment-model search kernel exists for this game (mcts.env_muzero_policy is det-MADN's); use "
                  "'random_agent', 'rule_based_agent' where the game has one, a MuZero agent, or for DOG 'rollout_agent'")
+# the same agent under gumbel_muzero_policy (mcts.env_gumbel_muzero_policy), det-MADN's second environment-search seat
+GUMBEL_MCTS_AGENT = "gumbel_mcts_agent"
+_NO_GUMBEL_CLASSIC = ("the Gumbel environment-model search (mcts.env_gumbel_muzero_policy) is det-MADN's: mctx has no "
+                      "Gumbel policy with chance nodes, so classic MADN's network-free seat is "
+                      "'stochastic_mcts_agent'; its other named seats are 'rule_based_agent' and 'random_agent'")
+_NO_GUMBEL_DOG = ("the Gumbel environment-model search (mcts.env_gumbel_muzero_policy) is det-MADN's: DOG's hidden "
+                  "hands have no environment-model search kernel (its network-free seat is 'rollout_agent')")
 # classic MADN's network-free MCTS seat (stochastic.env_stochastic_muzero_policy: the same construction with chance
 # nodes for the die; rollout cap of MADN/classic_madn.py's rollout, also 300)
 STOCHASTIC_MCTS_AGENT = "stochastic_mcts_agent"
@@ -121,13 +131,14 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
     """One batch of games, agent at seat 0 (+2 with teams), random elsewhere.  ``net=None`` makes the
     agent random too (the baseline).  ``search="puct"``: the agent searches with mcts.muzero_policy at temperature 0
     without root noise.  ``net="mcts_agent"``: the network-free MCTS agent (mcts.env_muzero_policy with rollouts of
-    at most ``rollout_steps`` turns, keyed by the game's index).  Returns wins at seat 0, per-seat wins and pins in
-    goal."""
+    at most ``rollout_steps`` turns, keyed by the game's index); ``net="gumbel_mcts_agent"``: the same agent under the
+    Gumbel policy (mcts.env_gumbel_muzero_policy).  Returns wins at seat 0, per-seat wins and pins in goal."""
     skw = _search_kwargs(search)
     if isinstance(net, str):
         net = _seat(_Det, net, 0, seed, device)
-        if net != MCTS_AGENT:
-            raise ValueError(f"play_vs_random: the agent is a network, None or {MCTS_AGENT!r}, not {net!r}")
+        if net not in (MCTS_AGENT, GUMBEL_MCTS_AGENT):
+            raise ValueError(f"play_vs_random: the agent is a network, None, {MCTS_AGENT!r} or {GUMBEL_MCTS_AGENT!r}, "
+                             f"not {net!r}")
     r = dict(RULES if rules is None else rules)
     teams = bool(r.get("enable_teams", False)) and num_players == 4
     P = num_players
@@ -141,6 +152,7 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
     gen = torch.Generator(device=device)
     gen.manual_seed(seed)
     ws = _workspace(_Det, [net], num_games, num_simulations, device) if net is not None else None
+    env_search = _Det.gumbel_env_search if net == GUMBEL_MCTS_AGENT else _Det.env_search
     mws = _mcts_workspace(_Det, [net], num_games, num_simulations, device)
     for turn in range(max_turns):
         active = env.done == 0
@@ -154,9 +166,8 @@ def play_vs_random(net: N.DeviceNet | None, num_games: int, num_players: int = 4
         mover = active & has
         ag = (mover & agent_seat).nonzero().flatten() if net is not None else mover.new_zeros(0, dtype=torch.long)
         rd = (mover & ~agent_seat).nonzero().flatten() if net is not None else mover.nonzero().flatten()
-        if ag.numel() and net == MCTS_AGENT:
-            act[ag] = _Det.env_search(env.take(ag), ag, num_simulations, max_depth, 0.0, seed, turn, mws,
-                                      rollout_steps)
+        if ag.numel() and isinstance(net, str):
+            act[ag] = env_search(env.take(ag), ag, num_simulations, max_depth, 0.0, seed, turn, mws, rollout_steps)
         elif ag.numel():
             act[ag] = _Det.search(net, env.take(ag), bits[ag], None, num_simulations, max_depth, 0.0, seed, turn, ws,
                                   skw)
@@ -292,6 +303,7 @@ class _Game:
     actions of a gathered sub-batch, ``scripted`` those of the whole batch."""
     REFUSED = {MCTS_AGENT: _NO_ENV_MODEL}      # named agents the game cannot play -> why
     ENV_SEAT = None                            # the name of the game's environment-search seat, if it has one
+    GUMBEL_SEAT = None                         # the name of that seat under the Gumbel policy, if the game has one
     ROLLOUT_SEAT = None                        # the name of the game's root-level rollout seat, if it has one
 
     @classmethod
@@ -318,6 +330,7 @@ class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
     REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET}
     ENV_SEAT = MCTS_AGENT
+    GUMBEL_SEAT = GUMBEL_MCTS_AGENT
     workspace = staticmethod(M.SearchWorkspace)
     env_workspace = staticmethod(M.EnvSearchWorkspace)
     scripted = staticmethod(policy_action)
@@ -347,12 +360,20 @@ class _Det(_Game):
                                      game_id=gid, workspace=mws)
         return out.action
 
+    @staticmethod
+    def gumbel_env_search(sub, gid, S, D, temperature, seed, turn, mws, rollout_steps=MCTS_ROLLOUT_STEPS):
+        """The 'gumbel_mcts_agent' seat: gumbel_muzero_policy over the real environment, ``temperature`` its Gumbel
+        scale, keyed by the games' ids."""
+        out, _ = M.env_gumbel_muzero_policy(sub, S, D, temperature, rollout_steps=rollout_steps, seed=seed, turn=turn,
+                                            game_id=gid, workspace=mws)
+        return out.action
+
 
 class _Classic(_Game):
     """play_eval_loop_jitted's body_fn (evaluate_agent_stochastic.py:754-900): throw_die (its dice_probabilities,
     soft lock aware) before the agents move."""
     env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
-    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC}
+    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC, GUMBEL_MCTS_AGENT: _NO_GUMBEL_CLASSIC}
     ENV_SEAT = STOCHASTIC_MCTS_AGENT
     scripted = staticmethod(classic_policy_action)
     env_workspace = staticmethod(ST.ClassicEnvSearchWorkspace)
@@ -400,7 +421,7 @@ class _Dog(_Game):
     # 806-action DOG mask cannot run, so the reference has no DOG rule-based agent to restate
     REFUSED = {"rule_based_agent": "MuZero_DOG/evaluate_agent.py's rule-based agent reshapes the 806-action mask to "
                                    "(4, 6) and cannot run; use 'random_agent' or a MuZero agent",
-               MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL}
+               MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, GUMBEL_MCTS_AGENT: _NO_GUMBEL_DOG}
     ROLLOUT_SEAT = ROLLOUT_AGENT
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
@@ -451,7 +472,7 @@ def _seat(game, a, i, seed, device):
     if isinstance(a, str):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
-        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.ROLLOUT_SEAT):
+        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.GUMBEL_SEAT, game.ROLLOUT_SEAT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
@@ -460,8 +481,8 @@ def _seat(game, a, i, seed, device):
 def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None,
           rollout_steps=MCTS_ROLLOUT_STEPS, rws=None, rollout=None) -> bool:
     """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
-    sub-batch of a seat (a network's, the game's environment-search seat's over the environment, or the game's
-    rollout seat's with the keywords ``rollout``), or a scripted agent's launch over the batch -- then the game's
+    sub-batch of a seat (a network's, the game's environment-search seat's over the environment -- PUCT or, for the
+    game's Gumbel seat, the Gumbel policy --, or the game's rollout seat's with the keywords ``rollout``), or a scripted agent's launch over the batch -- then the game's
     advance.  False, and nothing played, once every game is
     finished."""
     active = env.done == 0
@@ -479,6 +500,10 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
         if isinstance(a, str) and a == game.ENV_SEAT:
             idx = sel.nonzero().flatten()
             act[idx] = game.env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws, rollout_steps)
+        elif isinstance(a, str) and a == game.GUMBEL_SEAT:
+            idx = sel.nonzero().flatten()
+            act[idx] = game.gumbel_env_search(env.take(idx), gid[idx], S, D, temperature, seed, turn, mws,
+                                              rollout_steps)
         elif isinstance(a, str) and a == game.ROLLOUT_SEAT:
             idx = sel.nonzero().flatten()
             act[idx] = game.rollout_search(env.take(idx), gid[idx], seed, turn, rws,
@@ -497,8 +522,10 @@ def _workspace(game, seats, n, S, device):
 
 
 def _mcts_workspace(game, seats, n, S, device):
-    """The workspace of the game's environment-search seat, when one of the seats is that agent."""
-    if game.ENV_SEAT is None or not any(isinstance(x, str) and x == game.ENV_SEAT for x in seats):
+    """The workspace of the game's environment-search seats (one carve serves the PUCT and the Gumbel seat), when one
+    of the seats is such an agent."""
+    names = [x for x in (game.ENV_SEAT, game.GUMBEL_SEAT) if x is not None]
+    if not any(isinstance(x, str) and x in names for x in seats):
         return None
     return game.env_workspace(n, S, device)
 
@@ -554,8 +581,9 @@ def evaluate_agent_parallel(agents, batch_size: int = 20, num_simulations: int =
                             rule_agent: dict | None = None, device="cuda", *, search: str = "gumbel") -> dict:
     """evaluate_agent_parallel (evaluate_agent.py:253-311): `agents` = the four seats (player indices 0-3),
     each a DeviceNet, None (a MuZero agent with randomly initialised params), 'rule_based_agent',
-    'random_agent' or 'mcts_agent' (the network-free MCTS over the environment, mcts.env_muzero_policy with S / D,
-    temperature and no root noise).  4 x batch_size games, block i started by player i
+    'random_agent', 'mcts_agent' (the network-free MCTS over the environment, mcts.env_muzero_policy with S / D,
+    temperature and no root noise) or 'gumbel_mcts_agent' (the same agent under the Gumbel policy,
+    mcts.env_gumbel_muzero_policy with S / D and temperature as its Gumbel scale).  4 x batch_size games, block i started by player i
     (jnp.repeat(arange(4), batch_size)), at most 2000 turns; MuZero seats search with S / D / temperature (evaluate_agent.py:938-940 defaults) -- the
     Gumbel search, or with ``search="puct"`` mcts.muzero_policy without root noise.
     Returns winners[start][player] and average_progress[start][player] as the reference prints them, plus

@@ -238,6 +238,15 @@ class MuzEnvMctsCfg(ctypes.Structure):
     _fields_ = [("rollout_steps", ctypes.c_int32)]
 
 
+# muz_env_gumbel_cfg.qtransform: this, or MUZ_QT_MIN_MAX
+MUZ_QT_COMPLETED_MIX = 2
+
+
+class MuzEnvGumbelCfg(ctypes.Structure):
+    _fields_ = [("rollout_steps", ctypes.c_int32), ("qtransform", ctypes.c_int32), ("min_value", ctypes.c_float),
+                ("max_value", ctypes.c_float)]
+
+
 class MuzDogRolloutCfg(ctypes.Structure):
     _fields_ = [("rollouts", ctypes.c_int32), ("max_phases", ctypes.c_int32), ("rollout_steps", ctypes.c_int32),
                 ("determinize", ctypes.c_int32), ("seed", ctypes.c_uint64), ("turn", ctypes.c_int32)]
@@ -387,6 +396,9 @@ SIGNATURES = {
     "muz_detmadn_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzPuctCfg),
                                         ctypes.POINTER(MuzEnvMctsCfg), MuzDetSoA, vp, vp, vp, ctypes.c_int32, vp,
                                         ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
+    "muz_detmadn_gumbel_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzSearchCfg),
+                                               ctypes.POINTER(MuzEnvGumbelCfg), MuzDetSoA, vp, vp, ctypes.c_int32, vp,
+                                               ctypes.c_int64, vp, vp, vp, vp, vp, vp]),
     "muz_classic_mcts_tree_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.POINTER(MuzStochCfg)]),
     "muz_classic_mcts": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzStochCfg),
                                         ctypes.POINTER(MuzEnvMctsCfg), MuzClassicSoA, vp, vp, vp, ctypes.c_int32, vp,

@@ -6,7 +6,9 @@ second policy, the ``mctx.muzero_policy`` call it keeps commented (685-697: PUCT
 visit-count weights), is ``muzero_policy`` here: another persistent kernel (csrc/puct_search.hip) on the same
 workspace, chosen with ``policy="puct"``.  ``env_muzero_policy`` is the reference's network-free agent
 (MADN/deterministic_madn.py:481-589): the same ``muzero_policy`` with the det-MADN environment as its model and random
-rollouts as leaf values (csrc/env_mcts.hip), on a workspace of its own.
+rollouts as leaf values (csrc/env_mcts.hip), on a workspace of its own; ``env_gumbel_muzero_policy`` is the same agent
+under ``gumbel_muzero_policy`` (csrc/env_gumbel.hip), the call the reference drives
+(MADN/simulate_deterministicMADN.py:12-35), on that workspace.
 """
 from __future__ import annotations
 
@@ -193,6 +195,55 @@ def env_muzero_policy(env, num_simulations, max_depth, temperature=0.0, *, rollo
     _L.check(lib.muz_detmadn_mcts(env.rules, cfg, mcfg, env.soa(), _L.ptr(dn), _L.ptr(g), _L.ptr(gid), B,
                                   _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action), _L.ptr(weights),
                                   _L.ptr(value), _L.ptr(visits), _L.ptr(qvalues), _L.stream_ptr()), "muz_detmadn_mcts")
+    out = (PolicyOutput(action, weights), value)
+    return out + (visits, qvalues) if summary else out
+
+
+GUMBEL_QTRANSFORMS = {"completed_by_mix_value": _L.MUZ_QT_COMPLETED_MIX, "min_max": _L.MUZ_QT_MIN_MAX}
+
+
+def env_gumbel_muzero_policy(env, num_simulations, max_depth, temperature=0.0, *, rollout_steps=300, seed, turn,
+                             game_id=None, workspace: EnvSearchWorkspace | None = None, summary=False,
+                             qtransform="completed_by_mix_value", max_num_considered=16, value_scale=0.5,
+                             maxvisit_init=50.0, min_value=-1.0, max_value=1.0, gumbel=None):
+    """The network-free agent under the Gumbel policy, as the reference drives it (MADN/simulate_deterministicMADN.py:
+    12-35 run_gumbel: mctx.gumbel_muzero_policy over root_fn / recurrent_fn of MADN/deterministic_madn.py:481-589):
+    env_muzero_policy's model -- the det-MADN environment itself, prior logits 100 legal + 200 winning, random-rollout
+    leaf values of at most ``rollout_steps`` turns -- searched as gumbel_muzero_policy searches a network (sequential
+    halving at the root, completed Q-values, every node masked), one persistent kernel (csrc/env_gumbel.hip) on the
+    states of ``env`` (a detmadn.DetMADNState, read only) and env_muzero_policy's workspace.
+    ``qtransform``: "completed_by_mix_value" (gumbel_muzero_policy's here, with ``value_scale`` / ``maxvisit_init``) or
+    "min_max" (the reference's call, qtransform_by_min_max(``min_value``, ``max_value``)).  ``temperature`` is the
+    Gumbel scale as in gumbel_muzero_policy (0: a deterministic agent); ``gumbel`` = explicit, already scaled noise
+    [B, 24], or None to draw it on device from (seed, game_id, turn).  The semantics both parents leave open are fixed
+    in include/muz.h (muz_detmadn_gumbel_mcts); parity with the reference is unpinned.  A game that is finished or has
+    no legal action is not searched: action -1, weights 0, value 0.
+    Returns what env_muzero_policy returns: (PolicyOutput, root_value), with ``summary`` also visit_counts (int32
+    [B, 24]) and qvalues (fp32 [B, 24]; unvisited children 0)."""
+    from . import detmadn as _E
+    if not isinstance(env, _E.DetMADNState):
+        raise TypeError("env_gumbel_muzero_policy searches det-MADN states (detmadn.DetMADNState): no "
+                        f"environment-model kernel exists for {type(env).__name__}")
+    if qtransform not in GUMBEL_QTRANSFORMS:
+        raise ValueError(f"unknown qtransform {qtransform!r} (one of {sorted(GUMBEL_QTRANSFORMS)})")
+    lib = _L.load()
+    B = env.batch
+    dev = env.board.device
+    cfg = make_cfg(num_simulations, max_depth, temperature, max_num_considered, value_scale, maxvisit_init, seed, turn)
+    gcfg = _L.MuzEnvGumbelCfg(int(rollout_steps), GUMBEL_QTRANSFORMS[qtransform], float(min_value), float(max_value))
+    if workspace is None or not workspace.fits(B, num_simulations):
+        workspace = EnvSearchWorkspace(B, num_simulations, dev)
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    weights = torch.empty((B, _E.ACTIONS), dtype=torch.float32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    visits = torch.empty((B, _E.ACTIONS), dtype=torch.int32, device=dev) if summary else None
+    qvalues = torch.empty((B, _E.ACTIONS), dtype=torch.float32, device=dev) if summary else None
+    g = None if gumbel is None else gumbel.to(device=dev, dtype=torch.float32).contiguous()
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).contiguous()
+    _L.check(lib.muz_detmadn_gumbel_mcts(env.rules, cfg, gcfg, env.soa(), _L.ptr(g), _L.ptr(gid), B,
+                                         _L.ptr(workspace.tree), _L.nbytes(workspace.tree), _L.ptr(action),
+                                         _L.ptr(weights), _L.ptr(value), _L.ptr(visits), _L.ptr(qvalues),
+                                         _L.stream_ptr()), "muz_detmadn_gumbel_mcts")
     out = (PolicyOutput(action, weights), value)
     return out + (visits, qvalues) if summary else out
 

@@ -552,6 +552,42 @@ int muz_detmadn_mcts(const muz_rules* rules /*host*/, const muz_puct_cfg* cfg /*
                      int32_t* action, float* action_weights, float* root_value, int32_t* visit_counts,
                      float* qvalues, void* stream);
 
+/* ---- Gumbel network-free MCTS agent for det-MADN: gumbel_muzero_policy over the real environment ---------
+ * The call the reference drives (MADN/simulate_deterministicMADN.py:12-35 run_gumbel: mctx.gumbel_muzero_policy over
+ * root_fn / recurrent_fn of MADN/deterministic_madn.py:481-589 with qtransform_by_min_max(-1, 1)).  The model is
+ * muz_detmadn_mcts's, whole (legal, wins, prior logits 100 legal + 200 wins, transition with passes, reward and
+ * discount, rollout values and their keys); the search is muz_gumbel_search's (sequential halving over
+ * min(max_num_considered, legal count) root actions, completed Q-values, softmax - visit share inside; no Dirichlet
+ * noise, no tie-break uniform, every argmax the first maximum), with every node masked as in muz_detmadn_mcts: the
+ * prior logit is FMIN outside the node's mask and the interior score -inf there; a node with mask 0 counts as all 24
+ * actions legal.  Parity with the reference is UNPINNED as for muz_detmadn_mcts; the definition is
+ * tests/_env_gumbel.py, which the kernel (csrc/env_gumbel.hip) equals bit for bit.
+ * A root state that is done or has no legal action is not searched: action -1, weights 0, value 0. */
+#define MUZ_QT_COMPLETED_MIX 2     /* qtransform_completed_by_mix_value(value_scale, maxvisit_init), rescaled */
+typedef struct muz_env_gumbel_cfg {
+  int32_t rollout_steps;   /* as muz_env_mcts_cfg: 300; 0 = every leaf value is 0; at most 1000 */
+  int32_t qtransform;      /* MUZ_QT_COMPLETED_MIX (muz_gumbel_search's) or MUZ_QT_MIN_MAX (the reference's call) */
+  float min_value;         /* -1 (MUZ_QT_MIN_MAX only) */
+  float max_value;         /* 1  (MUZ_QT_MIN_MAX only) */
+} muz_env_gumbel_cfg;
+/* state is read only.  The workspace is muz_detmadn_mcts's (muz_detmadn_mcts_tree_bytes for the same
+ * num_simulations), so one workspace serves both agents.  gumbel [n][24] already scaled, or NULL to draw it on device
+ * as gumbel_scale times the counter RNG's draw of (seed, game_id, turn); game_id [n] (nullable: identity) feeds that
+ * counter and the rollouts' keys.  Outputs: action [n], action_weights [n][24] (softmax of the masked prior +
+ * completed Q), root_value [n], and search_tree.summary()'s visit_counts [n][24] / qvalues [n][24] (each nullable;
+ * unvisited children report 0).  After the call the first n int32 of the workspace hold each game's number of rollout
+ * turns.
+ * MUZ_E_UNSUPPORTED: S or D outside the limits, max_num_considered < 1, a negative (or NaN) gumbel_scale, value_scale
+ * or maxvisit_init, rollout_steps outside 0..1000, an unknown qtransform, max_value <= min_value, rules the det-MADN
+ * entry points refuse.  MUZ_E_INVALID: a null pointer, a workspace shorter than muz_detmadn_mcts_tree_bytes or not
+ * 16-byte aligned, state.stride < n.  Checked before any launch; n == 0 returns MUZ_OK; stream-ordered, no global
+ * state. */
+int muz_detmadn_gumbel_mcts(const muz_rules* rules /*host*/, const muz_search_cfg* cfg /*host*/,
+                            const muz_env_gumbel_cfg* gcfg /*host*/, muz_detmadn_soa state, const float* gumbel,
+                            const int32_t* game_id, int32_t n, void* workspace, int64_t workspace_bytes,
+                            int32_t* action, float* action_weights, float* root_value, int32_t* visit_counts,
+                            float* qvalues, void* stream);
+
 /* ---- self-play (MuZero_det_MADN/game_agent.py:50-192) ----------------------------------------------
  * Trajectory buffers [n][T] per game, T = max_steps, mirroring play_batch_of_games_jitted's dict
  * (game_agent.py:158-169); obs is stored int8 (values 0..4, the reference keeps them as fp32). */
