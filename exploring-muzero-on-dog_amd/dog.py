@@ -16,7 +16,9 @@ jax threefry; ``oracle/dog.py:engine_shuffle_keys`` restates them for the parity
 reference's ``encode_board`` is a stub (dog.py:1264-1272), so there is no DOG observation here.
 
 ``rollout_policy`` is the network-free rollout agent (csrc/dog_rollout.hip): the reference has no DOG agent that
-runs, so it is this engine's own and parity-unpinned; ``tests/_dog_rollout.py`` defines it.
+runs, so it is this engine's own and parity-unpinned; ``tests/_dog_rollout.py`` defines it.  ``greedy_policy`` is the
+one-ply greedy agent and ``afterstate_features`` the per-action board features it scores (csrc/dog_greedy.hip), the
+engine's own in the same way; ``tests/_dog_greedy.py`` defines them.
 """
 from __future__ import annotations
 
@@ -269,6 +271,57 @@ def rollout_policy(env, rollouts: int = 4, *, max_phases: int = 10, rollout_step
           _L.ptr(visits), _L.ptr(wins), _L.ptr(turns), B, _L.ptr(workspace.buf), _L.nbytes(workspace.buf),
           _L.stream_ptr())
     return (action, value, visits, wins, turns) if summary else action
+
+
+# ---- the one-ply greedy agent (csrc/dog_greedy.hip; include/muz.h, DOG greedy agent) ---------------------------------
+GREEDY_FEATURES = ("advance", "setback", "goal", "out", "hit", "win")
+GREEDY_DEFAULTS = dict(advance=1, setback=1, goal=20, out=15, hit=10, win=1000, temperature=0.25)
+
+
+def _greedy(env, name, w, temperature, seed, turn, game_id, want_scores, want_features):
+    if not isinstance(env, DOGState):
+        raise TypeError(f"{name} scores the afterstates of a DOG state (dog.DOGState), not {type(env).__name__}")
+    B, dev = env.batch, env.board.device
+    cfg = _L.MuzDogGreedyCfg((ctypes.c_int32 * 6)(*[int(x) for x in w]), float(temperature), ctypes_u64(seed),
+                             int(turn))
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    scores = torch.empty((B, ACTIONS), dtype=torch.int32, device=dev) if want_scores else None
+    features = torch.empty((B, ACTIONS, 6), dtype=torch.int32, device=dev) if want_features else None
+    _call("muz_dog_greedy_action", env.rules, ctypes.byref(cfg), env.soa(), _L.ptr(gid), _L.ptr(action),
+          _L.ptr(scores), _L.ptr(features), B, _L.stream_ptr())
+    return action, scores, features
+
+
+def afterstate_features(env) -> torch.Tensor:
+    """The six board features of every legal action's afterstate (int32 [B, 806, 6]: advance, setback, goal, out, hit,
+    win; 0 for an illegal action and for the swap phase's card choices): env_step tried once per legal action on the
+    real environment, without the deal it may ask for, and the board it leads to compared with the root's (include/muz.h,
+    DOG greedy agent; the definition is tests/_dog_greedy.py).  One launch (muz_dog_greedy_action with all weights 0);
+    ``env`` is not changed."""
+    return _greedy(env, "afterstate_features", (0,) * 6, 0.0, 0, 0, None, False, True)[2]
+
+
+def greedy_policy(env, *, weights: dict | None = None, temperature: float | None = None, seed: int, turn: int,
+                  game_id: torch.Tensor | None = None, summary: bool = False):
+    """The one-ply greedy agent's action for every game of ``env`` (int32 [B]; -1 for a finished game or one without a
+    legal action): every legal action is tried once on the real environment and scored by the board it leads to,
+    score = sum of ``weights`` (a dict over GREEDY_FEATURES; missing keys take GREEDY_DEFAULTS; integers in
+    [-32768, 32767]) times ``afterstate_features``; at ``temperature`` 0 the first action with the greatest score, else
+    the argmax of score / temperature plus the scripted agents' Gumbel draw, keyed by ``seed``, ``turn`` and
+    ``game_id`` (default: the position in the batch), so both are required (muz_dog_greedy_action; the semantics are in
+    include/muz.h, the definition is tests/_dog_greedy.py -- the reference has no DOG agent that runs, parity is
+    unpinned).  One launch; ``env`` is not changed.  With ``summary`` returns (action, scores int32 [B, 806] --
+    INT32_MIN for an illegal action --, features int32 [B, 806, 6])."""
+    v = dict(GREEDY_DEFAULTS)
+    unknown = set(weights or {}) - set(GREEDY_FEATURES)
+    if unknown:
+        raise ValueError(f"unknown greedy weights {sorted(unknown)} (the features are {GREEDY_FEATURES})")
+    v.update(weights or {})
+    t = v["temperature"] if temperature is None else temperature
+    action, scores, features = _greedy(env, "greedy_policy", [v[k] for k in GREEDY_FEATURES], t, seed, turn, game_id,
+                                       summary, summary)
+    return (action, scores, features) if summary else action
 
 
 # ---- action <-> move helpers (dog.py:1133-1262), host side ---------------------------------------------

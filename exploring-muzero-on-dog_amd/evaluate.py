@@ -22,6 +22,9 @@
   'rollout_agent'               DOG's network-free seat (DOG only): a root-level Monte-Carlo search over the real
                                 environment with re-drawn hidden cards, dog.rollout_policy (the reference has no DOG
                                 agent that runs; parity unpinned).
+  'greedy_agent'                DOG's cheap scripted seat (DOG only): every legal action tried once on the real
+                                environment and scored by the board it leads to, dog.greedy_policy over the whole
+                                batch (the reference's rule-based DOG agent cannot run; parity unpinned).
   policy_action                 the random agent (770-775) and the rule-based agent (777-864) as one device
                                 kernel (muz_detmadn_policy_action), sampling by Gumbel-max on the counter RNG.
 
@@ -81,6 +84,13 @@ _NO_ROLLOUT_DET = ("the rollout agent (dog.rollout_policy) is DOG's: det-MADN's 
                    "other named seats are 'rule_based_agent' and 'random_agent'")
 _NO_ROLLOUT_CLASSIC = ("the rollout agent (dog.rollout_policy) is DOG's: classic MADN's network-free seat is "
                        "'stochastic_mcts_agent'; its other named seats are 'rule_based_agent' and 'random_agent'")
+# DOG's scripted seat (dog.greedy_policy: one ply over the real environment, scored on the board); its parameters are
+# dog.GREEDY_DEFAULTS
+GREEDY_AGENT = "greedy_agent"
+_NO_GREEDY_DET = ("the greedy agent (dog.greedy_policy) is DOG's, whose reference rule-based agent cannot run: "
+                  "det-MADN's scripted seat is its own 'rule_based_agent'")
+_NO_GREEDY_CLASSIC = ("the greedy agent (dog.greedy_policy) is DOG's, whose reference rule-based agent cannot run: "
+                      "classic MADN's scripted seat is its own 'rule_based_agent'")
 
 # classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
 # defaults: no dice rethrow)
@@ -305,6 +315,7 @@ class _Game:
     ENV_SEAT = None                            # the name of the game's environment-search seat, if it has one
     GUMBEL_SEAT = None                         # the name of that seat under the Gumbel policy, if the game has one
     ROLLOUT_SEAT = None                        # the name of the game's root-level rollout seat, if it has one
+    GREEDY_SEAT = None                         # the name of the game's one-ply greedy scripted seat, if it has one
 
     @classmethod
     def reset(cls, n, sp, seed, device, r):
@@ -328,7 +339,7 @@ class _Game:
 
 class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
-    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET}
+    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET, GREEDY_AGENT: _NO_GREEDY_DET}
     ENV_SEAT = MCTS_AGENT
     GUMBEL_SEAT = GUMBEL_MCTS_AGENT
     workspace = staticmethod(M.SearchWorkspace)
@@ -373,7 +384,8 @@ class _Classic(_Game):
     """play_eval_loop_jitted's body_fn (evaluate_agent_stochastic.py:754-900): throw_die (its dice_probabilities,
     soft lock aware) before the agents move."""
     env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
-    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC, GUMBEL_MCTS_AGENT: _NO_GUMBEL_CLASSIC}
+    REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC, GUMBEL_MCTS_AGENT: _NO_GUMBEL_CLASSIC,
+               GREEDY_AGENT: _NO_GREEDY_CLASSIC}
     ENV_SEAT = STOCHASTIC_MCTS_AGENT
     scripted = staticmethod(classic_policy_action)
     env_workspace = staticmethod(ST.ClassicEnvSearchWorkspace)
@@ -423,6 +435,7 @@ class _Dog(_Game):
                                    "(4, 6) and cannot run; use 'random_agent' or a MuZero agent",
                MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, GUMBEL_MCTS_AGENT: _NO_GUMBEL_DOG}
     ROLLOUT_SEAT = ROLLOUT_AGENT
+    GREEDY_SEAT = GREEDY_AGENT
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
     rollout_workspace = staticmethod(DOG.RolloutWorkspace)
@@ -450,6 +463,12 @@ class _Dog(_Game):
 
     @staticmethod
     def scripted(env, legal, mode, seed, turn, agent, gid):
+        """'random_agent', or the 'greedy_agent' seat: dog.greedy_policy over the whole batch with the parameters
+        ``agent`` (a dict over dog.GREEDY_DEFAULTS' keys; None: the defaults), keyed by the games' ids."""
+        if mode == GREEDY_AGENT:
+            a = dict(agent or {})
+            temperature = a.pop("temperature", None)
+            return DOG.greedy_policy(env, weights=a, temperature=temperature, seed=seed, turn=turn, game_id=gid)
         return DOG.random_action(legal, seed=seed, turn=turn)
 
     @staticmethod
@@ -472,7 +491,8 @@ def _seat(game, a, i, seed, device):
     if isinstance(a, str):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
-        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.GUMBEL_SEAT, game.ROLLOUT_SEAT):
+        if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.GUMBEL_SEAT, game.ROLLOUT_SEAT,
+                     game.GREEDY_SEAT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
@@ -671,17 +691,21 @@ def compare_agents_statistically_classic(agent1, agent2, num_games: int = 1000, 
 def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: int = DOG_SIMULATIONS,
                                 max_depth: int = DOG_DEPTH, temperature: float = DOG_TEMPERATURE, seed: int = 0,
                                 rules: dict | None = None, max_turns: int = 2000, device="cuda", *, rollouts: int = 4,
-                                rollout_steps: int = MCTS_ROLLOUT_STEPS, determinize: bool = True) -> dict:
+                                rollout_steps: int = MCTS_ROLLOUT_STEPS, determinize: bool = True,
+                                greedy: dict | None = None) -> dict:
     """evaluate_agent_parallel (MuZero_DOG/evaluate_agent.py:255-313) with play_n_games_for_eval_jitted /
     play_eval_loop_jitted (315-527): `agents` = the four seats, each the DOG slice's MuZero (a DeviceDogNet or its
     flat params; None = randomly initialised params; run_muzero_mcts at A = 806, S 100, D 50, temperature 0.2),
-    'random_agent' (do_random: a uniform legal action) or 'rollout_agent' (the network-free root-level Monte-Carlo
+    'random_agent' (do_random: a uniform legal action), 'greedy_agent' (dog.greedy_policy: every legal action tried once
+    on the real environment and scored by the board it leads to, with the weights and temperature of ``greedy``, a dict
+    over dog.GREEDY_DEFAULTS' keys -- None: the defaults; keyed by seed, turn and the game's index) or
+    'rollout_agent' (the network-free root-level Monte-Carlo
     search dog.rollout_policy with ``rollouts`` playouts per action and phase of at most ``rollout_steps`` turns, the
     hidden cards re-drawn when ``determinize``; keyed by seed, turn and the game's index); 4 x batch_size games, block i started by player i, at most
     2000 turns; a game without a legal action applies no_step.  Every game steps in its own lane each turn (a finished
     game's lane applies no_step, which leaves its pins alone), so a game's deals are keyed by its own index.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals.
     Win-rate parity is unpinned: the reference's DOG networks and inference functions are `pass`."""
-    return _four_seats(_Dog, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns, None,
+    return _four_seats(_Dog, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns, greedy,
                        device, {}, report_turns=True,
                        rollout=dict(rollouts=rollouts, rollout_steps=rollout_steps, determinize=determinize))

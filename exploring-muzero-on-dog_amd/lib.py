@@ -252,6 +252,11 @@ class MuzDogRolloutCfg(ctypes.Structure):
                 ("determinize", ctypes.c_int32), ("seed", ctypes.c_uint64), ("turn", ctypes.c_int32)]
 
 
+class MuzDogGreedyCfg(ctypes.Structure):
+    _fields_ = [("w", ctypes.c_int32 * 6), ("temperature", ctypes.c_float), ("seed", ctypes.c_uint64),
+                ("turn", ctypes.c_int32)]
+
+
 class MuzSearchCfg(ctypes.Structure):
     _fields_ = [("num_simulations", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("max_num_considered", ctypes.c_int32), ("value_scale", ctypes.c_float),
@@ -329,6 +334,8 @@ SIGNATURES = {
     "muz_dog_rollout_bytes": (ctypes.c_int64, [ctypes.c_int32]),
     "muz_dog_rollout_search": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzDogRolloutCfg), MuzDogSoA,
                                               vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp]),
+    "muz_dog_greedy_action": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzDogGreedyCfg), MuzDogSoA,
+                                             vp, vp, vp, vp, ctypes.c_int32, vp]),
     "muz_classic_reset": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, ctypes.c_int32, vp]),
     "muz_classic_reset_seeded": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, vp, ctypes.c_int32, vp]),
     "muz_classic_set_die": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, vp, ctypes.c_int32, vp]),

@@ -345,6 +345,49 @@ int muz_dog_rollout_search(const muz_rules* rules /*host*/, const muz_dog_rollou
                            int32_t* wins /* [n][806], nullable */, uint32_t* rollout_turns /* [n], nullable */,
                            int32_t n, void* ws, int64_t ws_bytes, void* stream);
 
+/* ---- DOG greedy agent: one ply over the real environment, scored on the board (csrc/dog_greedy.hip) ---------------
+ * DOG's cheap scripted opponent.  The reference's rule-based DOG agent cannot run, so this agent is the engine's own
+ * and parity with the reference is UNPINNED; the definition is tests/_dog_greedy.py, which the kernel equals bit for
+ * bit in every integer (features, scores, the temperature-0 action).  For one root game with its game_id, cfg.turn and
+ * cfg.seed:
+ *   m = the current player; the side of seat p is p & 1 with teams, else p; ME = the seats on m's side, OP = the other
+ *   seats below num_players; C = the bits of muz_dog_legal's mask, ascending (empty for a finished game).
+ *   For a in C: after = env_step(root, a) WITHOUT the deal the step may ask for (only the board and the pins of
+ *   `after` are read, and a deal changes neither).  Swap-phase actions (792..805) leave the board alone: they are not
+ *   stepped and their features are 0.
+ *   prog(s, p) = calculate_progress (MuZero_DOG/evaluate_agent.py, the measure the DOG result tables print): p's pins
+ *   rotated to p's view (home -> pin - 5, track -> (pin - (40 / num_players) p) mod 40 - must_traverse_start, goal ->
+ *   40 + offset), sorted, matched greedily to the cells 40..43 (four times the smallest |pin - cell| of the rows and
+ *   columns left, first index on ties), the distances summed: an exact integer.
+ *   features[a][0..5], b = root, a = after (int32; 0 for an action outside C):
+ *     0 advance  sum over ME of prog(b, p) - prog(a, p)
+ *     1 setback  sum over OP of prog(a, p) - prog(b, p)
+ *     2 goal     sum over ME of (pins >= 40 after - before)
+ *     3 out      sum over ME of (pins < 0 before - after)     (negative when a 7 sends an own pin home)
+ *     4 hit      sum over OP of (pins < 0 after - before)
+ *     5 win      +1 if dog_winners(after) is non-empty and holds a seat of ME, -1 if non-empty and not, else 0
+ *   scores[a] = sum_i w[i] features[a][i] (int32) for a in C, INT32_MIN elsewhere.
+ *   action: -1 if C is empty; temperature == 0: the smallest a with the greatest score; else the first a of C whose
+ *   v(a) = float32(scores[a]) / temperature + policy_gumbel(key, a) is strictly greatest (one IEEE division, one IEEE
+ *   add), key = seed ^ 0x9011C7A6E47 ^ mix64(game_id << 32 | turn): the stream and the draw of the det and classic
+ *   scripted agents (muz_detmadn_policy_action), extended to a < 806.  Nothing is keyed by the position in the batch.
+ */
+typedef struct muz_dog_greedy_cfg {
+  int32_t w[6];        /* advance, setback, goal, out, hit, win; each in [-32768, 32767] */
+  float temperature;   /* >= 0 and finite; 0 = the first argmax of the scores */
+  uint64_t seed;
+  int32_t turn;
+} muz_dog_greedy_cfg;
+/* One launch on `stream` (one workgroup per game), no workspace, no host synchronisation, safe to capture into a
+ * graph.  `state` is read only.  game_id null: 0..n-1.  scores [n][806] and features [n][806][6] may be null.  All
+ * checks come before the launch: MUZ_E_INVALID for a null rules / cfg / action / state field, a weight out of range, a
+ * negative or non-finite temperature, n < 0 or n > state.stride; MUZ_E_UNSUPPORTED for the rules the muz_dog_* entry
+ * points refuse; n == 0 is MUZ_OK with nothing launched. */
+int muz_dog_greedy_action(const muz_rules* rules /*host*/, const muz_dog_greedy_cfg* cfg /*host*/,
+                          muz_dog_soa state /* read only */, const int32_t* game_id /* null: 0..n-1 */,
+                          int32_t* action /* [n] */, int32_t* scores /* [n][806], nullable */,
+                          int32_t* features /* [n][806][6], nullable */, int32_t n, void* stream);
+
 /* ---- MuZero networks (MuZero_det_MADN/muzero_deterministic_madn.py) --------------------------
  * Dense layers used by the MFMA kernels take their kernel W[K][N] PACKED for
  * v_mfma_f32_16x16x4_f32 B-fragments: [group][K/16][lane 64][tile NT][j 4] (group = wave, see muz_tile_waves) with
