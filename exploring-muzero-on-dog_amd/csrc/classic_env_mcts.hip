@@ -5,11 +5,13 @@
 // The tree is k_stochastic_search's (stochastic.hip): decision nodes (a state with its die thrown, children = the 4
 // pins) alternate with chance nodes (afterstates, children = the 6 die outcomes), A' = 4 + 6 child slots per node
 // padded to 16, a chance node's (reward, discount) applied on its chance -> decision edges.  The simulation body is
-// tree.hpp's (walk, commit_expansion, commit_backup on a NarrowTree<16>), the geometry k_env_mcts's (env_mcts.hip): a
-// workgroup owns 16 games for the whole search, 32 lanes per game, lane a holds child slot a; root children in
-// registers, node statistics and the path in SearchLds, the children arrays in the workspace.  A game never leaves its
-// half wave, so the simulation loop has no workgroup barrier; wave_sync() is enough for the reason env_mcts.hip gives
-// (LDS and vector memory operations of one wave complete in order, only the compiler has to be held).
+// tree.hpp's (walk, commit_expansion, commit_backup on a NarrowTree<16>) and so is the muzero_policy frame around it
+// (fill_pb_table, root_noise_share, root_prior, puct_score for the decision nodes, final_gumbel, visit_policy), the
+// geometry k_env_mcts's (env_mcts.hip): a workgroup owns 16 games for the whole search, 32 lanes per game, lane a holds
+// child slot a; root children in registers, node statistics and the path in SearchLds, the children arrays in the
+// workspace (CEnvTree, env_model.hpp's carve at 16 slots per node).  A game never leaves its half wave, so the
+// simulation loop has no workgroup barrier; wave_sync() is enough for the reason env_model.hpp gives (LDS and vector
+// memory operations of one wave complete in order, only the compiler has to be held).
 //
 // The environment runs in lane 0 of a game's 32 lanes (classic.hpp is written one board per lane and a node has only
 // 4 actions to check): the working state is a ClsLane in registers, its board and the rollout's copy of the board are
@@ -25,60 +27,19 @@
 // built: 0 B scratch, 37,808 B LDS, 128 VGPRs, 4 waves per SIMD -- the last under __launch_bounds__(kThreads, 4);
 // without the bound the allocator takes 130 VGPRs and the occupancy drops to 3.
 #include "classic.hpp"
-#include "host_consts.hpp"
-#include "rng.hpp"
-#include "tree.hpp"
+#include "env_model.hpp"
 
 namespace muz {
 
 namespace {
 
-constexpr int kCA = 16;            // child slots per node (A' = 10 used), as stochastic.hip kSA
+// (CEnvTree = EnvTreeT<16>: the carve, 10 of a node's 16 child slots used as in stochastic.hip; wave_sync, side_of,
+// kMaxRollout, last_pin_wins, rollout_uniform, pick_kth_bit, outcome_for, env_prior_logit: the toolkit at the top of
+// env_model.hpp, shared with k_env_mcts and k_env_gumbel)
 constexpr int kPins = MUZ_CLASSIC_ACTIONS, kDie = MUZ_CHANCE_OUTCOMES, kCAp = kPins + kDie;
-constexpr int kCNodeRow = 64;      // bytes of a node's row in the workspace (28 used)
-constexpr int kCMaxRollout = 1000;
-constexpr unsigned long long kClassicRolloutStream = 0xC1A551CD1CEull;   // != env_mcts.hip kRolloutStream
+constexpr unsigned long long kClassicRolloutStream = 0xC1A551CD1CEull;   // != env_model.hpp kRolloutStream
 // a node's byte in LDS: bits 0-3 the decision node's mask, then its kind and what the expansion hands to the lanes
 enum : uint32_t { K_DEC = 16u, K_PASS = 32u, K_SOFT = 64u };
-
-struct CEnvArrays : TreeArrays {
-  int8_t* rows;
-  int32_t* turns;
-};
-// The carve: each game's count of rollout turns [n] (int32, read by the caller after the search), the six children
-// arrays of NarrowTree<16>, then 64 B per node for its state row.  No latent slots.
-struct CEnvTree : NarrowTree<kCA, CEnvArrays> {
-  __device__ __forceinline__ AS1 uint32_t* row(int g, int node) const {
-    return reinterpret_cast<AS1 uint32_t*>(gpw(this->rows) + ((size_t)g * N + node) * kCNodeRow);
-  }
-  static size_t head_bytes(int64_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
-  static size_t bytes(int64_t n, int N) { return head_bytes(n) + 6 * child_bytes(n, N) + (size_t)n * N * kCNodeRow; }
-  static CEnvTree carve(void* ws, int n, int N) {
-    char* p = (char*)ws;
-    CEnvTree t;
-    t.turns = (int32_t*)p;
-    p += head_bytes(n);
-    const size_t cb = child_bytes(n, N);
-    t.c_index = (int32_t*)p;
-    t.c_prior = (float*)(p + cb);
-    t.c_value = (float*)(p + 2 * cb);
-    t.c_visits = (int32_t*)(p + 3 * cb);
-    t.c_reward = (float*)(p + 4 * cb);
-    t.c_disc = (float*)(p + 5 * cb);
-    t.emb = nullptr;
-    t.rows = (int8_t*)(p + 6 * cb);
-    t.N = N;
-    return t;
-  }
-};
-
-// (env_mcts.hip wave_sync: a game's lanes hand LDS and tree words to each other inside their wave only)
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
-__device__ __forceinline__ int cside(const DetConsts& c, int p) { return has(c.flags, R_TEAMS) ? (p & 1) : p; }
 
 // A node's state row: words 0-3 the 16 pins, word 4 player | die | done | reward
 __device__ __forceinline__ void row_store(AS1 uint32_t* r, const ClsLane& s) {
@@ -113,7 +74,6 @@ __device__ __forceinline__ void row_load(const AS1 uint32_t* r, ClsLane& s) {
 // with the trial steps.
 __device__ __forceinline__ uint32_t cls_wins(const DetConsts& c, const ClsLane& s, const BoardView& b,
                                              uint32_t legal) {
-  const uint32_t F = c.flags;
   const int cp = sub_player(c, b, s.cp);
   const int g0 = goal_of(c, cp, 0), g3 = goal_of(c, cp, 3);
   int ng = 0, out = 0;
@@ -125,27 +85,7 @@ __device__ __forceinline__ uint32_t cls_wins(const DetConsts& c, const ClsLane& 
     out = in ? out : k;
   }
   if (ng != 3 || ((legal >> out) & 1u) == 0u) return 0u;
-  const int cur = cpin(s, cp, out);
-  const int tgt = cst(c.target, cp);
-  const int x = cur + s.die - tgt - (has(F, R_MUST_TRAVERSE) ? 1 : 0);
-  const int gx = goal_of(c, cp, jidx(x - 1, 4));
-  const bool A = (b.at(gx) != cp) && (has(F, R_JUMP_GOAL) || goal_path_free(c, b, cp, -1, x));
-  bool win = cur != -1 && 4 >= x && x > 0 && A && cur <= tgt;
-  // get_winner with player cp done as well
-  uint32_t d = 1u << cp;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) d |= player_done(c, b, p) ? (1u << p) : 0u;
-  if (has(F, R_TEAMS)) {
-    const bool t0 = (d & 1u) && (d & 4u), t1 = (d & 2u) && (d & 8u);
-    d = ((t0 && t1) || !(t0 || t1)) ? 0u : (t0 ? 0x5u : 0xAu);
-  }
-  win = win && ((d >> cp) & 1u);
-  return win ? (1u << out) : 0u;
-}
-
-// the rollout's uniform j of node `node_key` (key: the game's, see the kernel)
-__device__ __forceinline__ float rollout_u(unsigned long long key, int node_key, int j) {
-  return u24(mix64(key ^ mix64(((unsigned long long)(unsigned)node_key << 16) | (unsigned)j)));
+  return last_pin_wins(c, b, cp, cpin(s, cp, out), s.die) ? (1u << out) : 0u;
 }
 
 // A random rollout from state s (a copy; its board in `from`), played by one lane on the board copy `bd`: every turn
@@ -164,28 +104,18 @@ __device__ __forceinline__ float cls_rollout(const DetConsts& c, ClsLane s, cons
     if (i > 0 || !keep_die) {
       float p[6];
       cls_dice_probs(c, cls_soft_locked(c, s, b), p);
-      s.die = cls_choice(p, rollout_u(key, node_key, 2 * i));
+      s.die = cls_choice(p, rollout_uniform(key, node_key, 2 * i));
     }
     const uint32_t lm = cls_legal(c, s, b);
     if (lm == 0u) {
       s.cp = mod_small(s.cp + 1, c.P);
     } else {
       const uint32_t wm = cls_wins(c, s, b, lm);
-      const uint32_t cand = wm ? wm : lm;
-      const int cnt = __popc(cand);
-      int k = (int)(rollout_u(key, node_key, 2 * i + 1) * (float)cnt);
-      k = k >= cnt ? cnt - 1 : k;
-      uint32_t x = cand;
-      for (int j = 0; j < k; ++j) x &= x - 1;   // drop the k lowest set bits
-      cls_step_masked(c, s, b, __ffs(x) - 1, lm);
+      cls_step_masked(c, s, b, pick_kth_bit(wm ? wm : lm, rollout_uniform(key, node_key, 2 * i + 1)), lm);
     }
     ++turns;
   }
-  const uint32_t w = winners(c, b);
-  bool mine = false;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) mine |= ((w >> p) & 1u) && cside(c, p) == view;
-  return mine ? 1.f : (w ? -1.f : 0.f);
+  return outcome_for(c, b, view);
 }
 
 __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, PuctArgs pa, int rollout_steps,
@@ -216,11 +146,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
   const int ai = pin_lane ? a : 0;        // in-bounds alias for the other lanes
   const BoardView cur{s_board[row], 1};
 
-  if (tid() <= kMaxNodes) {
-    const float N = (float)tid();
-    const float pb_c = pa.pb_c_init + log_cr((N + pa.pb_c_base + 1.0f) / pa.pb_c_base);
-    s_pbtab[tid()] = sqrtf(N) * pb_c;
-  }
+  fill_pb_table(s_pbtab, pa);
   if (a == 0) {
     s_kind[row][0] = 0;
     s_wins[row] = 0u;
@@ -231,14 +157,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
   // policies.py stochastic_muzero_policy: _add_dirichlet_noise, _get_logits_from_probs, _mask_invalid_actions)
   int gid = 0, turns = 0;
   unsigned long long rkey = 0;
-  Kid rk;   // the root's children, in registers for the whole search (prior: the probability)
-  rk.ok = ok;
-  rk.prior = 0.f;
-  rk.value = 0.f;
-  rk.reward = 0.f;
-  rk.disc = 0.f;
-  rk.visits = 0;
-  rk.index = -1;
+  Kid rk = empty_kid(ok, 0.f);   // the root's children, in registers for the whole search (prior: the probability)
   if (valid) {
     gid = game_id ? game_id[g] : g;
     rkey = game_key(pa.seed ^ kClassicRolloutStream, gid, pa.turn);
@@ -259,7 +178,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
       if (lm != 0u) {   // a root that is finished or has no legal pin for its die is not searched
         s_wins[row] = cls_wins(c, s, cur, lm);
         row_store(T.row(g, 0), s);
-        const float v = cls_rollout(c, s, s_board[row], r_board[row], cside(c, s.cp), true, rkey, 0, rollout_steps,
+        const float v = cls_rollout(c, s, s_board[row], r_board[row], side_of(c, s.cp), true, rkey, 0, rollout_steps,
                                     turns);
         s_kind[row][0] = (uint8_t)(lm | K_DEC);
         L.visits[row][0] = 1;
@@ -273,18 +192,10 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
   {
     const uint32_t wm = s_wins[row];
     const bool inv = !pin_lane || ((lm0 >> a) & 1u) == 0u;
-    const float lgt = 100.f * (float)((lm0 >> ai) & 1u) + 200.f * (float)((wm >> ai) & 1u);
-    const float pr = row_softmax24(pin_lane ? lgt : 0.f, pin_lane);
-    float dn = 0.f;
-    if (dirichlet_in) {
-      dn = (valid && pin_lane) ? dirichlet_in[(size_t)g * A + ai] : 0.f;
-    } else if (pa.dir_frac != 0.f) {
-      dn = row_softmax24(pin_lane ? root_noise_log_gamma(pa.dir_alpha, pa.seed, gid, pa.turn, a) : 0.f, pin_lane);
-    }
-    const float noisy = (1.f - pa.dir_frac) * pr + pa.dir_frac * dn;
-    float lg = pin_lane ? log_cr(fmaxf(noisy, kTinyF)) : -INFINITY;
-    lg = lg - row_max(lg);
-    const float p0 = row_softmax24(inv ? kFMin : lg, pin_lane);
+    const float pr = row_softmax24(pin_lane ? env_prior_logit(lm0, wm, ai) : 0.f, pin_lane);
+    const float dn =
+        root_noise_share(dirichlet_in, (size_t)g * A + ai, valid && pin_lane, pin_lane, pa, gid, pa.turn, a);
+    const float p0 = root_prior(pr, dn, pa.dir_frac, inv, pin_lane);
     rk.prior = (live && pin_lane) ? p0 : 0.f;
   }
   wave_sync();
@@ -295,12 +206,11 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
       // ---------------- simulate (search.py simulate): walk from the root
       const WalkEnd w = walk(T, L, rk, pa.D, [&](const Kid& k, int node, int depth) -> float {
         const uint32_t kind = s_kind[row][node];
-        // a decision node: muzero_action_selection (value_score + policy_score + 1e-7 U) inside the node's mask
+        // a decision node: muzero_action_selection inside the node's mask
         const bool inv = !pin_lane || ((kind >> a) & 1u) == 0u;
-        const float vs = value_score<MUZ_QT_PARENT_SIBLINGS>(k, L.val[row][node], pa);
-        const float ps = s_pbtab[L.visits[row][node]] * k.prior / (float)(k.visits + 1);
         const float tb = tiebreak_uniform(pa.seed, gid, pa.turn, sim, depth, ai);
-        const float ds = inv ? -INFINITY : vs + ps + 1e-7f * tb;
+        const float ds =
+            puct_score<MUZ_QT_PARENT_SIBLINGS>(k, L.val[row][node], L.visits[row][node], s_pbtab, tb, inv, pa);
         // a chance node: argmax p / (n + 1) on the environment's own die probabilities
         const float cs = die_lane ? k.prior / (float)(k.visits + 1) : -INFINITY;
         return (kind & K_DEC) ? ds : cs;
@@ -319,13 +229,13 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
       uint32_t nk;
       if (pk & K_DEC) {
         // recurrent_fn: decision -> afterstate.  The chance node keeps (reward, discount) for its outgoing edges
-        const int mover = cside(c, s.cp);
+        const int mover = side_of(c, s.cp);
         int rw = 0;
         if (pk & K_PASS)
           s.cp = mod_small(s.cp + 1, c.P);
         else
           rw = cls_step_masked(c, s, cur, act, pk & 15u);
-        const float dc = s.done ? 0.f : (cside(c, s.cp) == mover ? 1.f : -1.f);
+        const float dc = s.done ? 0.f : (side_of(c, s.cp) == mover ? 1.f : -1.f);
         AS1 uint32_t* r = T.row(g, nx);
         row_store(r, s);
         tree_st(reinterpret_cast<AS1 float*>(r) + 5, (float)rw);
@@ -346,7 +256,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
         row_store(T.row(g, nx), s);
         nk = K_DEC | (lm ? lm : (K_PASS | 1u));   // without a legal pin: one action, pin 0, which passes
         v = s.done ? 0.f
-                   : cls_rollout(c, s, s_board[row], r_board[row], cside(c, s.cp), true, rkey, sim + 1, rollout_steps,
+                   : cls_rollout(c, s, s_board[row], r_board[row], side_of(c, s.cp), true, rkey, sim + 1, rollout_steps,
                                  turns);
       }
       s_kind[row][nx] = (uint8_t)nk;
@@ -361,8 +271,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
       const uint32_t nk = live ? s_kind[row][L.next[row]] : 0u;
       const uint32_t wm = s_wins[row];
       const bool inv = !pin_lane || ((nk >> a) & 1u) == 0u;
-      const float lgt = 100.f * (float)((nk >> ai) & 1u) + 200.f * (float)((wm >> ai) & 1u);
-      const float dp = row_softmax24(inv ? kFMin : lgt, pin_lane);
+      const float dp = row_softmax24(inv ? kFMin : env_prior_logit(nk, wm, ai), pin_lane);
       float p[6];
       cls_dice_probs(c, (nk & K_SOFT) != 0u, p);
       const float pc = (a == A) ? p[0] : ((a == A + 5) ? p[5] : p[1]);   // die 1, die 6, the equal middle four
@@ -380,35 +289,18 @@ __global__ __launch_bounds__(kThreads, 4) void k_classic_env_mcts(DetConsts c, P
   // ---------------- tail (_mask_tree(decision), summary().visit_probs, _apply_temperature, categorical as
   // argmax(logits + Gumbel); summary().visit_counts / qvalues)
   if (!valid) return;
-  const int vc = pin_lane ? rk.visits : 0;
-  const int tot = row_isum(vc);
-  const float w = (float)vc / (float)max(tot, 1);
-  float lw = pin_lane ? log_cr(w) : -INFINITY;
-  lw = (lw - row_max(lw)) / fmaxf(kTinyF, pa.temperature);
-  const float gmb = pin_lane ? (gumbel_in ? gumbel_in[(size_t)g * A + ai]
-                                          : gumbel_noise(pa.seed ^ 0xC2B2AE3D27D4EB4Full, gid, pa.turn, ai))
-                             : 0.f;
-  float sc = pin_lane ? lw + gmb : -INFINITY;
-  int bi = a;
-  row_argmax(sc, bi);
+  const float gmb = final_gumbel(gumbel_in, (size_t)g * A + ai, pin_lane, pa.seed, gid, pa.turn, ai);
+  const PolicyDraw pd = visit_policy(rk.visits, pin_lane, pa.temperature, gmb);
   if (pin_lane) {
-    out_weights[(size_t)g * A + a] = live ? w : 0.f;
-    if (out_visits) out_visits[(size_t)g * A + a] = vc;
+    out_weights[(size_t)g * A + a] = live ? pd.weight : 0.f;
+    if (out_visits) out_visits[(size_t)g * A + a] = rk.visits;
     if (out_q) out_q[(size_t)g * A + a] = rk.reward + rk.disc * rk.value;
   }
   if (a == 0) {
-    out_action[g] = live ? bi : -1;
+    out_action[g] = live ? pd.action : -1;
     out_value[g] = live ? fminf(1.f, fmaxf(-1.f, L.val[row][0])) : 0.f;
     T.turns[g] = turns;
   }
-}
-
-// muz_stoch_cfg's own settings (written so that a NaN is refused too)
-int check_stoch_cfg(const muz_stoch_cfg& cfg) {
-  if (!(cfg.dirichlet_fraction >= 0.f && cfg.dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
-  if (!(cfg.dirichlet_alpha > 0.f) || !(cfg.pb_c_base > 0.f) || !(cfg.temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
-  if (!(cfg.pb_c_init == cfg.pb_c_init)) return MUZ_E_UNSUPPORTED;
-  return MUZ_OK;
 }
 
 }  // namespace
@@ -433,25 +325,13 @@ int muz_classic_mcts(const muz_rules* rules, const muz_stoch_cfg* cfg, const muz
   const int rc = make_det_consts(rules, &c);
   if (rc) return rc;
   if (check_stoch_cfg(*cfg) || check_search_limits(cfg->num_simulations, cfg->max_depth)) return MUZ_E_UNSUPPORTED;
-  if (mcfg->rollout_steps < 0 || mcfg->rollout_steps > kCMaxRollout) return MUZ_E_UNSUPPORTED;
+  if (mcfg->rollout_steps < 0 || mcfg->rollout_steps > kMaxRollout) return MUZ_E_UNSUPPORTED;
   MUZ_HOST_CHECK(n >= 0 && state.stride >= n && workspace && action && action_weights && root_value);
   MUZ_HOST_CHECK(state.board && state.pins && state.current_player && state.done && state.reward && state.die);
   MUZ_HOST_CHECK(((uintptr_t)workspace & 15u) == 0 &&
                  workspace_bytes >= (int64_t)CEnvTree::bytes(n, cfg->num_simulations + 1));
   if (n == 0) return MUZ_OK;
-  PuctArgs pa;
-  pa.S = cfg->num_simulations;
-  pa.D = cfg->max_depth;
-  pa.qtransform = MUZ_QT_PARENT_SIBLINGS;
-  pa.min_value = -1.f;
-  pa.max_value = 1.f;
-  pa.dir_frac = cfg->dirichlet_fraction;
-  pa.dir_alpha = cfg->dirichlet_alpha;
-  pa.pb_c_init = cfg->pb_c_init;
-  pa.pb_c_base = cfg->pb_c_base;
-  pa.temperature = cfg->temperature;
-  pa.seed = cfg->seed;
-  pa.turn = cfg->turn;
+  const PuctArgs pa = make_puct_args(*cfg);
   const CEnvTree T = CEnvTree::carve(workspace, n, pa.S + 1);
   const dim3 grid((n + kRows - 1) / kRows);
   k_classic_env_mcts<<<grid, kThreads, 0, (hipStream_t)stream>>>(c, pa, mcfg->rollout_steps, state, dirichlet, gumbel,

@@ -8,7 +8,8 @@
 // the no-move passes, the prior 100 legal + 200 wins, the value a random rollout keyed by (seed, game, turn, node,
 // rollout turn)); the search is k_gumbel_search's (tree.hpp: sequential halving at the root, completed-Q, softmax -
 // visit share inside, no Dirichlet noise, no tie-break uniform, every argmax the first maximum).  A game never leaves
-// its half wave, so the simulation loop has no workgroup barrier, only wave_sync().
+// its half wave, so the simulation loop has no workgroup barrier, only wave_sync().  The root's empty children
+// (empty_kid) are tree.hpp's and the prior logit (env_prior_logit) env_model.hpp's, as in k_env_mcts.
 //
 // What the two parents leave open is fixed in tests/_env_gumbel.py, which this kernel equals bit for bit:
 //   mask        every node is masked as in k_env_mcts (mctx masks the root only): the prior logit is FMIN outside the
@@ -73,14 +74,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_env_gumbel(DetConsts c, SearchA
   uint32_t lb = 0;                        // the root's mask
   float gum = 0.f;
   float rpp = 0.f, rpm = 0.f;             // prior_probs of the root's children and its largest prior
-  Kid rk;   // the root's children, in registers for the whole search (prior: the logit)
-  rk.ok = ok;
-  rk.prior = kFMin;
-  rk.value = 0.f;
-  rk.reward = 0.f;
-  rk.disc = 0.f;
-  rk.visits = 0;
-  rk.index = -1;
+  Kid rk = empty_kid(ok, kFMin);   // the root's children, in registers for the whole search (prior: the logit)
   bool live = false;   // a root that is finished or has no legal action is not searched
   if (valid) {
     const int gid = game_id ? game_id[g] : g;
@@ -92,7 +86,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_env_gumbel(DetConsts c, SearchA
       if (a < kStateRow / 4) tree_st(T.row(g, 0) + a, reinterpret_cast<const uint32_t*>(cur.st)[a]);
       const float v = rollout(c, cur, roll, a, t, rkey, 0, ea.rollout_steps, turns);
       const bool inv = !ok || ((lb >> a) & 1u) == 0u;
-      const float l = ok ? 100.f * (float)((lb >> ai) & 1u) + 200.f * (float)((wm >> ai) & 1u) : -INFINITY;
+      const float l = ok ? env_prior_logit(lb, wm, ai) : -INFINITY;
       const float lm = row_max(l);
       rk.prior = inv ? kFMin : l - lm;
       if (ok)
@@ -161,8 +155,7 @@ __global__ __launch_bounds__(kThreads, 4) void k_env_gumbel(DetConsts c, SearchA
       if (!e.done) v = rollout(c, cur, roll, a, t, rkey, sim + 1, ea.rollout_steps, turns);
       // the new node keeps its prior logits
       const bool inv = !ok || (((e.legal ? e.legal : kAllActions) >> a) & 1u) == 0u;
-      const float lgt = 100.f * (float)((e.legal >> ai) & 1u) + 200.f * (float)((e.wins >> ai) & 1u);
-      commit_expansion(T, L, rk, sim, inv ? kFMin : lgt, v, e.reward, e.disc);
+      commit_expansion(T, L, rk, sim, inv ? kFMin : env_prior_logit(e.legal, e.wins, ai), v, e.reward, e.disc);
       if (a == 0) s_raw[row][nx] = (int8_t)v;
       // ---------------- backward (search.py backward) along the recorded path
       commit_backup(T, L, rk, v, e.reward, e.disc);

@@ -3,7 +3,8 @@
 // root_fn / recurrent_fn, driven by MADN/simulate_deterministicMADN.py:12-35; the same construction as
 // TicTacToe/mcts.py:9-23) as ONE persistent kernel per batched search.
 //
-// The geometry and the simulation body are k_puct_search's (tree.hpp): a workgroup owns 16 games for the whole search,
+// The geometry, the simulation body and the muzero_policy frame around it (pb_c table, noisy masked root prior, PUCT
+// score, visit-count tail) are k_puct_search's (tree.hpp): a workgroup owns 16 games for the whole search,
 // 32 lanes per game, lane a holds child a; root children in registers, node statistics and the path in SearchLds, the
 // children arrays in the workspace.  What differs is the expansion: instead of Dyn4 + Pred4 a node's embedding is its
 // 48-byte state row (kStateRow, kept in 64 B per node), the transition is env_step plus the no-move passes on the
@@ -26,8 +27,8 @@ namespace muz {
 
 namespace {
 
-// (EnvTree, GameRows, det_wins_g, node_legal, env_expand and rollout -- the environment as the search's model:
-// env_model.hpp, shared with k_env_gumbel)
+// (EnvTree, GameRows, det_wins_g, node_legal, env_prior_logit, env_expand and rollout -- the environment as the
+// search's model: env_model.hpp, shared with k_env_gumbel; its toolkit also with k_classic_env_mcts)
 
 template <int QT>
 __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa, int rollout_steps,
@@ -55,11 +56,7 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
   const int ai = ok ? a : 0;              // in-bounds alias for lanes a >= A
   const GameRows cur{s_state[row], s_board[row]}, roll{r_state[row], r_board[row]};
 
-  if (tid() <= kMaxNodes) {
-    const float N = (float)tid();
-    const float pb_c = pa.pb_c_init + log_cr((N + pa.pb_c_base + 1.0f) / pa.pb_c_base);
-    s_pbtab[tid()] = sqrtf(N) * pb_c;
-  }
+  fill_pb_table(s_pbtab, pa);
   det_rows_load<kRows>(c, st, g0, min(kRows, n - g0), s_board, s_state, t, kThreads);
   __syncthreads();
 
@@ -67,14 +64,7 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
   // _add_dirichlet_noise, _get_logits_from_probs, _mask_invalid_actions, instantiate_tree_from_root)
   int gid = 0, turns = 0;
   unsigned long long rkey = 0;
-  Kid rk;   // the root's children, in registers for the whole search (prior: the probability)
-  rk.ok = ok;
-  rk.prior = 0.f;
-  rk.value = 0.f;
-  rk.reward = 0.f;
-  rk.disc = 0.f;
-  rk.visits = 0;
-  rk.index = -1;
+  Kid rk = empty_kid(ok, 0.f);   // the root's children, in registers for the whole search (prior: the probability)
   bool live = false;   // a root that is finished or has no legal action is not searched
   if (valid) {
     gid = game_id ? game_id[g] : g;
@@ -86,18 +76,9 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
       if (a < kStateRow / 4) tree_st(T.row(g, 0) + a, reinterpret_cast<const uint32_t*>(cur.st)[a]);
       const float v = rollout(c, cur, roll, a, t, rkey, 0, rollout_steps, turns);
       const bool inv = !ok || ((lm >> a) & 1u) == 0u;
-      const float lgt = 100.f * (float)((lm >> ai) & 1u) + 200.f * (float)((wm >> ai) & 1u);
-      const float pr = row_softmax24(ok ? lgt : 0.f, ok);
-      float dn = 0.f;
-      if (dirichlet_in) {
-        dn = ok ? dirichlet_in[(size_t)g * A + ai] : 0.f;
-      } else if (pa.dir_frac != 0.f) {
-        dn = row_softmax24(ok ? root_noise_log_gamma(pa.dir_alpha, pa.seed, gid, pa.turn, a) : 0.f, ok);
-      }
-      const float noisy = (1.f - pa.dir_frac) * pr + pa.dir_frac * dn;
-      float lg = ok ? log_cr(fmaxf(noisy, kTinyF)) : -INFINITY;
-      lg = lg - row_max(lg);
-      rk.prior = row_softmax24(inv ? kFMin : lg, ok);
+      const float pr = row_softmax24(ok ? env_prior_logit(lm, wm, ai) : 0.f, ok);
+      const float dn = root_noise_share(dirichlet_in, (size_t)g * A + ai, ok, ok, pa, gid, pa.turn, a);
+      rk.prior = root_prior(pr, dn, pa.dir_frac, inv, ok);
       if (a == 0) {
         s_legal[row][0] = lm;
         L.visits[row][0] = 1;
@@ -112,13 +93,11 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
     if (live) {
       // ---------------- simulate (search.py simulate): walk from the root
       const WalkEnd w = walk(T, L, rk, pa.D, [&](const Kid& k, int node, int depth) -> float {
-        // muzero_action_selection: value_score + policy_score + 1e-7 U, masked by the node's mask
+        // muzero_action_selection, masked by the node's mask
         const uint32_t nm = s_legal[row][node];
         const bool inv = !ok || (((nm ? nm : kAllActions) >> a) & 1u) == 0u;
-        const float vs = value_score<QT>(k, L.val[row][node], pa);
-        const float ps = s_pbtab[L.visits[row][node]] * k.prior / (float)(k.visits + 1);
         const float tb = tiebreak_uniform(pa.seed, gid, pa.turn, sim, depth, ai);
-        return inv ? -INFINITY : vs + ps + 1e-7f * tb;
+        return puct_score<QT>(k, L.val[row][node], L.visits[row][node], s_pbtab, tb, inv, pa);
       });
       if (a == 0) L.hand_off(row, w, sim);
     }
@@ -134,8 +113,7 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
       if (!e.done) v = rollout(c, cur, roll, a, t, rkey, sim + 1, rollout_steps, turns);
       // the new node keeps its prior probabilities
       const bool inv = !ok || (((lm ? lm : kAllActions) >> a) & 1u) == 0u;
-      const float lgt = 100.f * (float)((lm >> ai) & 1u) + 200.f * (float)((wm >> ai) & 1u);
-      commit_expansion(T, L, rk, sim, row_softmax24(inv ? kFMin : lgt, ok), v, rw, dc);
+      commit_expansion(T, L, rk, sim, row_softmax24(inv ? kFMin : env_prior_logit(lm, wm, ai), ok), v, rw, dc);
       // ---------------- backward (search.py backward) along the recorded path
       commit_backup(T, L, rk, v, rw, dc);
     }
@@ -145,24 +123,15 @@ __global__ __launch_bounds__(kThreads) void k_env_mcts(DetConsts c, PuctArgs pa,
   // ---------------- tail (policies.py muzero_policy: summary().visit_probs, _apply_temperature, categorical as
   // argmax(logits + Gumbel); summary().visit_counts / qvalues)
   if (!valid) return;
-  const int vc = ok ? rk.visits : 0;
-  const int tot = row_isum(vc);
-  const float w = (float)vc / (float)max(tot, 1);
-  float lw = ok ? log_cr(w) : -INFINITY;
-  lw = (lw - row_max(lw)) / fmaxf(kTinyF, pa.temperature);
-  const float gmb =
-      ok ? (gumbel_in ? gumbel_in[(size_t)g * A + ai] : gumbel_noise(pa.seed ^ 0xC2B2AE3D27D4EB4Full, gid, pa.turn, ai))
-         : 0.f;
-  float sc = ok ? lw + gmb : -INFINITY;
-  int bi = a;
-  row_argmax(sc, bi);
+  const float gmb = final_gumbel(gumbel_in, (size_t)g * A + ai, ok, pa.seed, gid, pa.turn, ai);
+  const PolicyDraw pd = visit_policy(rk.visits, ok, pa.temperature, gmb);
   if (ok) {
-    out_weights[(size_t)g * A + a] = live ? w : 0.f;
-    if (out_visits) out_visits[(size_t)g * A + a] = vc;
+    out_weights[(size_t)g * A + a] = live ? pd.weight : 0.f;
+    if (out_visits) out_visits[(size_t)g * A + a] = rk.visits;
     if (out_q) out_q[(size_t)g * A + a] = rk.reward + rk.disc * rk.value;
   }
   if (a == 0) {
-    out_action[g] = live ? bi : -1;
+    out_action[g] = live ? pd.action : -1;
     out_value[g] = live ? L.val[row][0] : 0.f;
     T.turns[g] = turns;
   }

@@ -3,6 +3,8 @@
 // per node, a game's LDS rows, wins(s), the node mask, the expansion's transition (env_step plus the no-move passes)
 // and the random rollout.  One game per kRowLanes lanes, lane a holds action a; everything here is called by all the
 // lanes of a game together.  The semantics are fixed in tests/_env_mcts.py (see env_mcts.hip's head).
+// At the top, what k_classic_env_mcts (classic_env_mcts.hip) takes too: the carve (EnvTreeT), wave_sync, side_of, the
+// rollout cap, the tail of wins(s), the rollout's uniform, pick and outcome, and the prior logit.
 #pragma once
 #include "detmadn.hpp"
 #include "host_consts.hpp"
@@ -12,30 +14,33 @@
 namespace muz {
 inline namespace MUZ_NN_NS {   // (built on tid(): see the note at the top of nn.hpp)
 
-constexpr int kMaxPasses = 4;       // the turn head's fast-forward cap (selfplay.hip)
-constexpr int kNodeRow = 64;        // bytes of a node's state row in the workspace (kStateRow used)
-constexpr int kMaxRollout = 1000;
-constexpr unsigned long long kRolloutStream = 0x7011007D1CEull;
-constexpr uint32_t kAllActions = 0xFFFFFFu;
+// ---- the toolkit of every environment-as-model search, det (below) and classic (classic_env_mcts.hip) ---------------
+
+constexpr int kNodeRow = 64;        // bytes of a node's state row in the workspace (det: kStateRow used, classic: 28)
+constexpr int kMaxRollout = 1000;   // the entry points' bound on rollout_steps
 
 // The tree's own carve: each game's count of rollout turns [n] (int32, read by the caller after the search), the six
-// children arrays of NarrowTree<32>, then 64 B per node for its state row.  No latent slots.
+// children arrays of NarrowTree<APAD>, then 64 B per node for its state row.  No latent slots.
 struct EnvArrays : TreeArrays {
   int8_t* rows;
   int32_t* turns;
 };
-struct EnvTree : NarrowTree<32, EnvArrays> {
+template <int APAD>
+struct EnvTreeT : NarrowTree<APAD, EnvArrays> {
+  using Base = NarrowTree<APAD, EnvArrays>;
   __device__ __forceinline__ AS1 uint32_t* row(int g, int node) const {
-    return reinterpret_cast<AS1 uint32_t*>(gpw(this->rows) + ((size_t)g * N + node) * kNodeRow);
+    return reinterpret_cast<AS1 uint32_t*>(gpw(this->rows) + ((size_t)g * this->N + node) * kNodeRow);
   }
   static size_t head_bytes(int64_t n) { return ((size_t)n * 4 + 255) & ~(size_t)255; }
-  static size_t bytes(int64_t n, int N) { return head_bytes(n) + 6 * child_bytes(n, N) + (size_t)n * N * kNodeRow; }
-  static EnvTree carve(void* ws, int n, int N) {
+  static size_t bytes(int64_t n, int N) {
+    return head_bytes(n) + 6 * Base::child_bytes(n, N) + (size_t)n * N * kNodeRow;
+  }
+  static EnvTreeT carve(void* ws, int n, int N) {
     char* p = (char*)ws;
-    EnvTree t;
+    EnvTreeT t;
     t.turns = (int32_t*)p;
     p += head_bytes(n);
-    const size_t cb = child_bytes(n, N);
+    const size_t cb = Base::child_bytes(n, N);
     t.c_index = (int32_t*)p;
     t.c_prior = (float*)(p + cb);
     t.c_value = (float*)(p + 2 * cb);
@@ -48,6 +53,8 @@ struct EnvTree : NarrowTree<32, EnvArrays> {
     return t;
   }
 };
+using EnvTree = EnvTreeT<32>;    // det-MADN: 24 actions per node
+using CEnvTree = EnvTreeT<16>;   // classic: 4 pins + 6 die outcomes per node
 
 // A game's lanes hand LDS rows and tree words to each other inside their wave only: LDS and vector memory operations
 // of one wave complete in order, so the compiler alone has to be held (no cache action, no wait).
@@ -56,6 +63,62 @@ __device__ __forceinline__ void wave_sync() {
   __builtin_amdgcn_wave_barrier();
 }
 
+__device__ __forceinline__ int side_of(const DetConsts& c, int p) { return has(c.flags, R_TEAMS) ? (p & 1) : p; }
+
+// The shared tail of wins(s) (det_wins_g below, cls_wins): does player cp's last pin outside its goal, at cell `cur`
+// and moved m cells, land on a goal cell (env_step's new_pos of the det / classic step) and does get_winner, with cp
+// done as well, then name cp?
+__device__ __forceinline__ bool last_pin_wins(const DetConsts& c, const BoardView& b, int cp, int cur, int m) {
+  const uint32_t F = c.flags;
+  const int tgt = cst(c.target, cp);
+  const int x = cur + m - tgt - (has(F, R_MUST_TRAVERSE) ? 1 : 0);
+  const int gx = goal_of(c, cp, jidx(x - 1, 4));
+  const bool A = (b.at(gx) != cp) && (has(F, R_JUMP_GOAL) || goal_path_free(c, b, cp, -1, x));
+  const bool win = cur != -1 && 4 >= x && x > 0 && A && cur <= tgt;
+  // get_winner with player cp done as well
+  uint32_t d = 1u << cp;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) d |= player_done(c, b, p) ? (1u << p) : 0u;
+  if (has(F, R_TEAMS)) {
+    const bool t0 = (d & 1u) && (d & 4u), t1 = (d & 2u) && (d & 8u);
+    d = ((t0 && t1) || !(t0 || t1)) ? 0u : (t0 ? 0x5u : 0xAu);
+  }
+  return win && ((d >> cp) & 1u);
+}
+
+// A rollout's uniform j of node `node_key` (key: the game's), its pick among the candidate actions `cand` (!= 0) --
+// the k-th set bit, k = min(floor(u count), count - 1) -- and its outcome on board b seen from `side`
+__device__ __forceinline__ float rollout_uniform(unsigned long long key, int node_key, int j) {
+  return u24(mix64(key ^ mix64(((unsigned long long)(unsigned)node_key << 16) | (unsigned)j)));
+}
+__device__ __forceinline__ int pick_kth_bit(uint32_t cand, float u) {
+  const int cnt = __popc(cand);
+  int k = (int)(u * (float)cnt);
+  k = k >= cnt ? cnt - 1 : k;
+  uint32_t x = cand;
+  for (int j = 0; j < k; ++j) x &= x - 1;   // drop the k lowest set bits
+  return __ffs(x) - 1;
+}
+__device__ __forceinline__ float outcome_for(const DetConsts& c, const BoardView& b, int side) {
+  const uint32_t w = winners(c, b);
+  bool mine = false;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) mine |= ((w >> p) & 1u) && side_of(c, p) == side;
+  return mine ? 1.f : (w ? -1.f : 0.f);
+}
+
+// root_fn / recurrent_fn's prior logit of action ai under a node's legal and winning masks
+__device__ __forceinline__ float env_prior_logit(uint32_t legal, uint32_t wins, int ai) {
+#pragma clang fp contract(off)
+  return 100.f * (float)((legal >> ai) & 1u) + 200.f * (float)((wins >> ai) & 1u);
+}
+
+// ---- det-MADN -------------------------------------------------------------------------------------------------------
+
+constexpr int kMaxPasses = 4;       // the turn head's fast-forward cap (selfplay.hip)
+constexpr unsigned long long kRolloutStream = 0x7011007D1CEull;
+constexpr uint32_t kAllActions = 0xFFFFFFu;
+
 // The LDS rows of one game: its state row and its board
 struct GameRows {
   int8_t* st;
@@ -63,8 +126,6 @@ struct GameRows {
   __device__ __forceinline__ BoardView board() const { return BoardView{bd, 1}; }
   __device__ __forceinline__ LdsLane lane() const { return LdsLane{st, st[40], st[41], st[42]}; }
 };
-
-__device__ __forceinline__ int side_of(const DetConsts& c, int p) { return has(c.flags, R_TEAMS) ? (p & 1) : p; }
 
 // set_pins_on_board by the game's 32 lanes (rebuild_board's result: no two pins share a cell)
 __device__ __forceinline__ void rebuild_board_g(const DetConsts& c, const GameRows& r, int a) {
@@ -84,7 +145,6 @@ __device__ __forceinline__ void rebuild_board_g(const DetConsts& c, const GameRo
 // the trial steps.
 __device__ __forceinline__ uint32_t det_wins_g(const DetConsts& c, const LdsLane& s, const BoardView& b, int a, int t,
                                                uint32_t legal) {
-  const uint32_t F = c.flags;
   const int cp = sub_player(c, b, s.cp);
   const int g0 = goal_of(c, cp, 0), g3 = goal_of(c, cp, 3);
   int ng = 0, out = 0;
@@ -97,23 +157,7 @@ __device__ __forceinline__ uint32_t det_wins_g(const DetConsts& c, const LdsLane
   }
   const int i = a / 6, m = a % 6 + 1;
   bool win = a < 24 && ((legal >> a) & 1u) && ng == 3 && i == out;
-  if (win) {
-    const int cur = pin_of(s, cp, i);
-    const int tgt = cst(c.target, cp);
-    const int x = cur + m - tgt - (has(F, R_MUST_TRAVERSE) ? 1 : 0);
-    const int gx = goal_of(c, cp, jidx(x - 1, 4));
-    const bool A = (b.at(gx) != cp) && (has(F, R_JUMP_GOAL) || goal_path_free(c, b, cp, -1, x));
-    win = cur != -1 && 4 >= x && x > 0 && A && cur <= tgt;
-    // get_winner with player cp done as well
-    uint32_t d = 1u << cp;
-#pragma unroll
-    for (int p = 0; p < 4; ++p) d |= player_done(c, b, p) ? (1u << p) : 0u;
-    if (has(F, R_TEAMS)) {
-      const bool t0 = (d & 1u) && (d & 4u), t1 = (d & 2u) && (d & 8u);
-      d = ((t0 && t1) || !(t0 || t1)) ? 0u : (t0 ? 0x5u : 0xAu);
-    }
-    win = win && ((d >> cp) & 1u);
-  }
+  if (win) win = last_pin_wins(c, b, cp, pin_of(s, cp, i), m);
   const unsigned long long bal = __ballot(win);
   return (uint32_t)(bal >> (kRowLanes * ((t & 63) / kRowLanes))) & kAllActions;
 }
@@ -145,14 +189,7 @@ __device__ __forceinline__ float rollout(const DetConsts& c, const GameRows& fro
       if (lm == 0u) {
         det_nostep(c, s);
       } else {
-        const uint32_t cand = wm ? wm : lm;
-        const int cnt = __popc(cand);
-        const float u = u24(mix64(key ^ mix64(((unsigned long long)(unsigned)node_key << 16) | (unsigned)i)));
-        int k = (int)(u * (float)cnt);
-        k = k >= cnt ? cnt - 1 : k;
-        uint32_t x = cand;
-        for (int j = 0; j < k; ++j) x &= x - 1;   // drop the k lowest set bits
-        const int act = __ffs(x) - 1;
+        const int act = pick_kth_bit(wm ? wm : lm, rollout_uniform(key, node_key, i));
         det_step_masked(c, s, b, act / 6, act % 6 + 1, lm);
       }
       r.st[40] = (int8_t)s.cp;
@@ -162,11 +199,7 @@ __device__ __forceinline__ float rollout(const DetConsts& c, const GameRows& fro
     ++turns;
     wave_sync();
   }
-  const uint32_t w = winners(c, b);
-  bool mine = false;
-#pragma unroll
-  for (int p = 0; p < 4; ++p) mine |= ((w >> p) & 1u) && side_of(c, p) == side0;
-  return mine ? 1.f : (w ? -1.f : 0.f);
+  return outcome_for(c, b, side0);
 }
 
 // What the expansion of an edge gives (search.py expand's recurrent_fn, the environment): the edge's reward and

@@ -86,13 +86,15 @@ struct PuctArgs {
   const int32_t* key_game = nullptr;
   const int32_t* key_turn = nullptr;
 };
-static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
+// (the settings muz_puct_cfg and muz_stoch_cfg both have, under the same names)
+template <class Cfg>
+static inline PuctArgs puct_args_of(const Cfg& cfg, int qtransform, float min_value, float max_value) {
   PuctArgs pa;
   pa.S = cfg.num_simulations;
   pa.D = cfg.max_depth;
-  pa.qtransform = cfg.qtransform;
-  pa.min_value = cfg.min_value;
-  pa.max_value = cfg.max_value;
+  pa.qtransform = qtransform;
+  pa.min_value = min_value;
+  pa.max_value = max_value;
   pa.dir_frac = cfg.dirichlet_fraction;
   pa.dir_alpha = cfg.dirichlet_alpha;
   pa.pb_c_init = cfg.pb_c_init;
@@ -102,12 +104,28 @@ static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
   pa.turn = cfg.turn;
   return pa;
 }
+static inline PuctArgs make_puct_args(const muz_puct_cfg& cfg) {
+  return puct_args_of(cfg, cfg.qtransform, cfg.min_value, cfg.max_value);
+}
+// muz_classic_mcts (classic_env_mcts.hip) runs the same frame from a muz_stoch_cfg: mctx's default qtransform,
+// parent-and-siblings, between the value bounds -1 and 1
+static inline PuctArgs make_puct_args(const muz_stoch_cfg& cfg) {
+  return puct_args_of(cfg, MUZ_QT_PARENT_SIBLINGS, -1.f, 1.f);
+}
 // muz_puct_cfg's own settings, as every entry point that takes one refuses them (written so that a NaN is refused too)
 static inline int check_puct_cfg(const muz_puct_cfg& cfg) {
   if (cfg.qtransform != MUZ_QT_MIN_MAX && cfg.qtransform != MUZ_QT_PARENT_SIBLINGS) return MUZ_E_UNSUPPORTED;
   if (!(cfg.max_value > cfg.min_value)) return MUZ_E_UNSUPPORTED;
   if (!(cfg.dirichlet_fraction >= 0.f && cfg.dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
   if (!(cfg.dirichlet_alpha > 0.f) || !(cfg.pb_c_base > 0.f) || !(cfg.temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
+  return MUZ_OK;
+}
+// muz_stoch_cfg's own settings, as muz_classic_mcts refuses them (written so that a NaN is refused too;
+// muz_stochastic_search keeps its own checks)
+static inline int check_stoch_cfg(const muz_stoch_cfg& cfg) {
+  if (!(cfg.dirichlet_fraction >= 0.f && cfg.dirichlet_fraction <= 1.f)) return MUZ_E_UNSUPPORTED;
+  if (!(cfg.dirichlet_alpha > 0.f) || !(cfg.pb_c_base > 0.f) || !(cfg.temperature >= 0.f)) return MUZ_E_UNSUPPORTED;
+  if (!(cfg.pb_c_init == cfg.pb_c_init)) return MUZ_E_UNSUPPORTED;
   return MUZ_OK;
 }
 int launch_puct_search(const muz_net_w& w, const PuctArgs& pa, const float* root_logits, const float* root_value,

@@ -11,7 +11,9 @@
 //   tail    -- visit-count action weights, temperature, Gumbel-max draw (as k_stochastic_search's).
 // A node's children keep softmax(prior logits) instead of the logits (c_prior, written once at expansion): the walks
 // read the probabilities only.  sqrt(N) pb_c(N) is tabulated once per search for every visit count a node can reach.
-#include "rng.hpp"
+// The root prior, the score and the tail are tree.hpp's muzero_policy frame (fill_pb_table, root_noise_share,
+// root_prior, puct_score, final_gumbel, visit_policy), shared with k_env_mcts and k_classic_env_mcts; the noise is
+// not drawn at dirichlet_fraction 0, where its share is multiplied by 0.
 #include "tree.hpp"
 
 namespace muz {
@@ -40,24 +42,13 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
   const bool ok = a < A;
   const int ai = ok ? a : 0;              // in-bounds alias for lanes a >= A
 
-  if (tid() <= kMaxNodes) {
-    const float N = (float)tid();
-    const float pb_c = pa.pb_c_init + log_cr((N + pa.pb_c_base + 1.0f) / pa.pb_c_base);
-    s_pbtab[tid()] = sqrtf(N) * pb_c;
-  }
+  fill_pb_table(s_pbtab, pa);
 
   // ---------------- root (policies.py muzero_policy: _add_dirichlet_noise, _get_logits_from_probs,
   // _mask_invalid_actions; then instantiate_tree_from_root)
   unsigned lb = 0;
   int gid = 0, gturn = pa.turn;
-  Kid rk;   // the root's children, in registers for the whole search (prior: the probability)
-  rk.ok = ok;
-  rk.prior = 0.f;
-  rk.value = 0.f;
-  rk.reward = 0.f;
-  rk.disc = 0.f;
-  rk.visits = 0;
-  rk.index = -1;
+  Kid rk = empty_kid(ok, 0.f);   // the root's children, in registers for the whole search (prior: the probability)
   bool inv = true;
   if (valid) {
     lb = legal[g];
@@ -67,16 +58,8 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     gturn = pa.key_turn ? pa.key_turn[gid] : pa.turn;
     inv = !ok || ((lb >> a) & 1u) == 0u;
     const float pr = row_softmax24(ok ? root_logits[(size_t)g * A + ai] : 0.f, ok);
-    float dn = 0.f;
-    if (dirichlet_in) {
-      dn = ok ? dirichlet_in[(size_t)g * A + ai] : 0.f;
-    } else {
-      dn = row_softmax24(ok ? root_noise_log_gamma(pa.dir_alpha, pa.seed, gid, gturn, a) : 0.f, ok);
-    }
-    const float noisy = (1.f - pa.dir_frac) * pr + pa.dir_frac * dn;
-    float lg = ok ? log_cr(fmaxf(noisy, kTinyF)) : -INFINITY;
-    lg = lg - row_max(lg);
-    rk.prior = row_softmax24(inv ? kFMin : lg, ok);
+    const float dn = root_noise_share(dirichlet_in, (size_t)g * A + ai, ok, ok, pa, gid, gturn, a);
+    rk.prior = root_prior(pr, dn, pa.dir_frac, inv, ok);
     AS1 float* e0 = T.e(g, 0);
     for (int c = a; c < LAT; c += kRowLanes) e0[c] = root_emb[(size_t)g * LAT + c];
     if (a == 0) {
@@ -99,11 +82,9 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
     // ---------------- simulate (search.py simulate): walk from the root
     if (valid) {
       const WalkEnd w = walk(T, L, rk, pa.D, [&](const Kid& k, int node, int depth) -> float {
-        // muzero_action_selection: value_score + policy_score + 1e-7 U, masked at the root
-        const float vs = value_score<QT>(k, L.val[row][node], pa);
-        const float ps = s_pbtab[L.visits[row][node]] * k.prior / (float)(k.visits + 1);
+        // muzero_action_selection, masked at the root
         const float tb = tiebreak_uniform(pa.seed, gid, gturn, sim, depth, ai);
-        return (!ok || (depth == 0 && inv)) ? -INFINITY : vs + ps + 1e-7f * tb;
+        return puct_score<QT>(k, L.val[row][node], L.visits[row][node], s_pbtab, tb, !ok || (depth == 0 && inv), pa);
       });
       // expand's inputs (parent embedding, FiLM rows of the action): issued by the game's own lanes now
       din = dyn_load(wl->dyn, A, T.e(g, w.node), w.act);
@@ -135,20 +116,11 @@ __global__ __launch_bounds__(kThreads, 1) void k_puct_search(
   // ---------------- tail (policies.py muzero_policy: summary().visit_probs, _apply_temperature, categorical as
   // argmax(logits + Gumbel))
   if (valid) {
-    const int vc = ok ? rk.visits : 0;
-    const int tot = row_isum(vc);
-    const float w = (float)vc / (float)max(tot, 1);
-    float lw = ok ? log_cr(w) : -INFINITY;
-    lw = (lw - row_max(lw)) / fmaxf(kTinyF, pa.temperature);
-    const float gmb =
-        ok ? (gumbel_in ? gumbel_in[(size_t)g * A + ai] : gumbel_noise(pa.seed ^ 0xC2B2AE3D27D4EB4Full, gid, gturn, ai))
-           : 0.f;
-    float sc = ok ? lw + gmb : -INFINITY;
-    int bi = a;
-    row_argmax(sc, bi);
-    if (ok) out_weights[(size_t)g * A + a] = w;
+    const float gmb = final_gumbel(gumbel_in, (size_t)g * A + ai, ok, pa.seed, gid, gturn, ai);
+    const PolicyDraw pd = visit_policy(rk.visits, ok, pa.temperature, gmb);
+    if (ok) out_weights[(size_t)g * A + a] = pd.weight;
     if (a == 0) {
-      out_action[g] = bi;
+      out_action[g] = pd.action;
       out_value[g] = L.val[row][0];
     }
   }

@@ -3,7 +3,10 @@
 // one simulation body -- SearchLds (the per-row LDS state), NarrowTree::kid (a node's children), walk (the selection
 // loop around the kernel's score), commit_expansion and commit_backup -- and differ in their root, score and tail.
 // k_env_mcts (env_mcts.hip) is k_puct_search's body and score (value_score, row_softmax24 below) around an expansion
-// that steps the environment instead of the networks, on a carve of its own.
+// that steps the environment instead of the networks, on a carve of its own.  The muzero_policy frame around the body
+// -- the pb_c table, the noisy masked root prior, the PUCT score and the visit-count tail (fill_pb_table,
+// root_noise_share, root_prior, puct_score, final_gumbel, visit_policy below) -- is one definition for k_puct_search,
+// k_env_mcts and k_classic_env_mcts (classic_env_mcts.hip).
 // k_env_gumbel (env_gumbel.hip) is that expansion (env_model.hpp) under k_gumbel_search's scores (prior_probs,
 // completed_q below).
 // k_stochastic_search shares the tree layout and row_argmax and keeps its own walk, expansion and one-lane backup
@@ -13,6 +16,7 @@
 // the host entry points read them too.
 #pragma once
 #include "launch.hpp"
+#include "rng.hpp"
 #include "nn.hpp"
 
 namespace muz {
@@ -116,6 +120,81 @@ __device__ __forceinline__ float row_softmax24(float x, bool ok) {
   const float m = row_max(ok ? x : -INFINITY);
   const float e = ok ? exp_cr(x - m) : 0.f;
   return e / row_sum24(e);
+}
+
+// ---- the muzero_policy frame of the PUCT kernels (k_puct_search, k_env_mcts, k_classic_env_mcts): what surrounds the
+// simulation body.  ok: the lane holds one of the policy's actions (classic: a pin lane).  The helpers take the noise
+// keys (gid, turn) as arguments -- k_puct_search's turn is per game -- and each call site keeps its own control flow
+// around them: row_max, row_softmax24, row_isum and row_argmax are collectives over the game's lanes.
+
+// A root child before the first simulation
+__device__ __forceinline__ Kid empty_kid(bool ok, float prior) { return Kid{prior, 0.f, 0.f, 0.f, 0, -1, ok}; }
+
+// tab[N] = sqrt(N) * pb_c(N) for every visit count N = 0..kMaxNodes a node can reach, once per search (by the
+// workgroup's first threads; the caller's barrier follows)
+__device__ __forceinline__ void fill_pb_table(float* tab, const PuctArgs& pa) {
+#pragma clang fp contract(off)
+  if (tid() <= kMaxNodes) {
+    const float N = (float)tid();
+    const float pb_c = pa.pb_c_init + log_cr((N + pa.pb_c_base + 1.0f) / pa.pb_c_base);
+    tab[tid()] = sqrtf(N) * pb_c;
+  }
+}
+
+// This lane's share of the root's Dirichlet noise: the caller's array (read by the lanes with `rd`) or, drawn on the
+// device, the softmax of the row's log-gammas.  No draw at fraction 0: root_prior multiplies the share by it, and
+// 0 * (a softmax term, finite and >= 0) is the +0 that 0 * 0 is.
+__device__ __forceinline__ float root_noise_share(const float* dirichlet_in, size_t at, bool rd, bool ok,
+                                                  const PuctArgs& pa, int gid, int turn, int a) {
+  if (dirichlet_in) return rd ? dirichlet_in[at] : 0.f;
+  if (pa.dir_frac == 0.f) return 0.f;
+  return row_softmax24(ok ? root_noise_log_gamma(pa.dir_alpha, pa.seed, gid, turn, a) : 0.f, ok);
+}
+
+// policies.py _add_dirichlet_noise, _get_logits_from_probs, _mask_invalid_actions and the tree's softmax: the masked
+// root prior probability from the prior probability pr and the noise share dn (inv: the action is not legal)
+__device__ __forceinline__ float root_prior(float pr, float dn, float dir_frac, bool inv, bool ok) {
+#pragma clang fp contract(off)
+  const float noisy = (1.f - dir_frac) * pr + dir_frac * dn;
+  float lg = ok ? log_cr(fmaxf(noisy, kTinyF)) : -INFINITY;
+  lg = lg - row_max(lg);
+  return row_softmax24(inv ? kFMin : lg, ok);
+}
+
+// muzero_action_selection's score of child k of a decision node with value nv and nvis visits: value_score +
+// policy_score + 1e-7 U (tb: the tie-break uniform), -inf where the lane may not be chosen (inv)
+template <int QT>
+__device__ __forceinline__ float puct_score(const Kid& k, float nv, int nvis, const float* tab, float tb, bool inv,
+                                            const PuctArgs& pa) {
+#pragma clang fp contract(off)
+  const float vs = value_score<QT>(k, nv, pa);
+  const float ps = tab[nvis] * k.prior / (float)(k.visits + 1);
+  return inv ? -INFINITY : vs + ps + 1e-7f * tb;
+}
+
+// The final draw's Gumbel value of action ai: the caller's array or the counter RNG's policy stream
+__device__ __forceinline__ float final_gumbel(const float* gumbel_in, size_t at, bool ok, unsigned long long seed,
+                                              int gid, int turn, int ai) {
+  return ok ? (gumbel_in ? gumbel_in[at] : gumbel_noise(seed ^ 0xC2B2AE3D27D4EB4Full, gid, turn, ai)) : 0.f;
+}
+
+// muzero_policy's tail (summary().visit_probs, _apply_temperature, categorical as argmax(logits + Gumbel)): this
+// lane's action weight from its root visits and the row's drawn action
+struct PolicyDraw {
+  float weight;
+  int action;
+};
+__device__ __forceinline__ PolicyDraw visit_policy(int visits, bool ok, float temperature, float gmb) {
+#pragma clang fp contract(off)
+  const int vc = ok ? visits : 0;
+  const int tot = row_isum(vc);
+  const float w = (float)vc / (float)max(tot, 1);
+  float lw = ok ? log_cr(w) : -INFINITY;
+  lw = (lw - row_max(lw)) / fmaxf(kTinyF, temperature);
+  float sc = ok ? lw + gmb : -INFINITY;
+  int bi = tsub();
+  row_argmax(sc, bi);
+  return PolicyDraw{w, bi};
 }
 
 // qtransform_completed_by_mix_value's prior_probs of this lane's child, softmax(prior logits) clamped at the smallest

@@ -97,7 +97,7 @@ def timing(parent=False):
     base = mid(ms["k_env_mcts"])
     for name in kinds:
         s, t = mid(ms[name]), mid(turns[name])
-        print(f"[{who}] {name}: {s:.2f} ms per batched search (spread {min(ms[name]):.2f}-{max(ms[name]):.2f} over "
+        print(f"[{who}] {name}: {s:.3f} ms per batched search (spread {min(ms[name]):.3f}-{max(ms[name]):.3f} over "
               f"the repetitions), {B / (s * 1e-3) / 1e3:.1f} k searches/s, {B * S / (s * 1e-3) / 1e6:.2f} M "
               f"simulations/s, {t} rollout turns, {t / (s * 1e-3) / 1e6:.1f} M rollout env-steps/s; tree alone "
               f"{mid(tree[name]):.2f} ms; time over k_env_mcts's {s / base:.3f}")

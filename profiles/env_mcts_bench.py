@@ -4,11 +4,13 @@ same batch (one launch per env-step of every game, with and without the observat
 search: 3 repetitions, HIP events, medians.  A rollout turn does that round's work (legal mask, pick, env_step or
 no_step) plus the wins mask, and none of its launch, SoA load / store or encode.
 
-    python profiles/env_mcts_bench.py            # writes profiles/env_mcts_bench.log
+    python profiles/env_mcts_bench.py [--parent-lib PATH]     # writes profiles/env_mcts_bench.log
+
+--parent-lib: a libmuz.so built from the parent commit; the same measurement runs first through it, in a process of
+its own (MUZ_LIB), so the log holds both commits' figures from one session.
 
 The measuring step runs in a child process under its own time limit; this process never opens the GPU."""
 import os
-import subprocess
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -92,7 +94,7 @@ def child():
     rate = t / (s * 1e-3)
     tree = sorted(ms["tree"])[REPS // 2]
     per_game = t / B
-    print(f"search: {s:.2f} ms per batched search, {B / (s * 1e-3) / 1e3:.1f} k searches/s, "
+    print(f"search: {s:.3f} ms per batched search, {B / (s * 1e-3) / 1e3:.1f} k searches/s, "
           f"{B * S / (s * 1e-3) / 1e6:.2f} M simulations/s")
     print(f"rollouts: {t} turns per batched search (counted on the device: {t / (B * (S + 1)):.1f} per rollout of at "
           f"most {ROLLOUT}), {rate / 1e6:.1f} M rollout env-steps/s (the search's whole time charged to them)")
@@ -112,16 +114,8 @@ def child():
           f"visited {float((w > 0).sum(1).float().mean()):.2f}, mean root value {float(rv.mean()):+.3f}")
 
 
-def main():
-    r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child"], capture_output=True, text=True,
-                       timeout=300)
-    sys.stdout.write(r.stdout)
-    sys.stderr.write(r.stderr)
-    if r.returncode == 0:
-        with open(LOG, "w") as f:
-            f.write(r.stdout)
-    return r.returncode
-
-
 if __name__ == "__main__":
-    sys.exit(child() if "--child" in sys.argv else main())
+    if "--child" in sys.argv:
+        sys.exit(child())
+    import _parent_lib
+    sys.exit(_parent_lib.main(__file__, LOG, sys.argv))
