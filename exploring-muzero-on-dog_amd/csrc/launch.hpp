@@ -28,6 +28,14 @@ static inline int check_search_call(int num_simulations, int max_depth, int n, c
   return MUZ_OK;
 }
 
+// MUZ_RING_ADDR (read per launch): the dense layers' weight addressing in k_gumbel_search (default form),
+// k_root_dense and k_recurrent -- unset or 1: a scalar base and one 32-bit lane offset (nn.hpp, SB); 0: the form
+// before, 64-bit addresses per lane, kept for A/B runs and tests/test_gpu_ring_addressing.py
+static inline bool ring_scalar_base() {
+  const char* e = getenv("MUZ_RING_ADDR");
+  return !e || atoi(e) != 0;
+}
+
 struct SearchArgs {
   int S, D, max_considered;
   float value_scale, maxvisit_init, gumbel_scale;

@@ -608,7 +608,8 @@ int launch_dense0(const muz_dense& d0, int n, const int* n_dev, float* conv, hip
 
 // Rest of RepresentationNetwork2 + PredictionNetwork4 on 16-game tiles.  NW = muz_net_w (det) or
 // muz_classic_net_w (classic): both carry obs_channels, num_actions, repr and pred.
-template <class NW>
+// SB: the dense layers' weight addressing (nn.hpp; MUZ_RING_ADDR, read per launch)
+template <class NW, bool SB>
 __global__ __launch_bounds__(kThreads) void k_root_dense(NW Wt, const float* __restrict__ obs,
                                                     const float* __restrict__ convout, int n,
                                                     const int* __restrict__ n_dev, float* prior_logits, float* value,
@@ -623,7 +624,7 @@ __global__ __launch_bounds__(kThreads) void k_root_dense(NW Wt, const float* __r
   const int row = trow(), sub = tsub();
   const int gr = g0 + row;
   const bool valid = gr < n;
-  Pf pf;
+  PfT<SB> pf;
   repr16<NT256, true>(W->repr, obs, Wt.obs_channels, convout, g0, n, a, pf, &W->pred.rb[0].d0, LAT, LAT);
   __syncthreads();
   minmax16(a.T, LD);
@@ -639,6 +640,7 @@ __global__ __launch_bounds__(kThreads) void k_root_dense(NW Wt, const float* __r
 }
 
 // recurrent_inference_fn on 16-row tiles.
+template <bool SB>
 __global__ __launch_bounds__(kThreads) void k_recurrent(muz_net_w Wt, const int32_t* __restrict__ action,
                                                    const float* __restrict__ emb, int n, float* reward,
                                                    float* discount, float* prior_logits, float* value,
@@ -653,7 +655,7 @@ __global__ __launch_bounds__(kThreads) void k_recurrent(muz_net_w Wt, const int3
   const AS4 muz_net_w* W = kernarg0<muz_net_w>();   // == Wt, read through the kernarg segment
   const int ar = valid ? action[gr] : 0;
   const DynIn din = dyn_load(W->dyn, A, valid ? gp(emb) + (size_t)gr * LAT : nullptr, ar);
-  Pf pf;
+  PfT<SB> pf;
   pf_issue<NT256>(pf, &W->dyn.d3, LAT, LAT);
   dyn16<NT256>(W->dyn, A, din, ar, a, pf, &W->pred.rb[0].d0, LAT, LAT);
   if (valid) {
@@ -720,7 +722,10 @@ static int launch_root_impl(const NW& w, const float* obs, int n, const int* n_d
   if (rc) return rc;
   rc = launch_dense0(w.repr.d0, n, n_dev, conv, s);
   if (rc) return rc;
-  k_root_dense<NW><<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, obs, conv, n, n_dev, logits, value, emb);
+  if (ring_scalar_base())
+    k_root_dense<NW, true><<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, obs, conv, n, n_dev, logits, value, emb);
+  else
+    k_root_dense<NW, false><<<(n + kRows - 1) / kRows, kThreads, 0, s>>>(w, obs, conv, n, n_dev, logits, value, emb);
   return muz_last_launch_error();
 }
 
@@ -771,8 +776,12 @@ int muz_nets_recurrent(const muz_net_w* w, const int32_t* action, const float* e
   if (rc) return rc;
   MUZ_HOST_CHECK(n >= 0 && action && embedding && reward && discount && prior_logits && value && next_embedding);
   if (n == 0) return MUZ_OK;
-  k_recurrent<<<(n + kRows - 1) / kRows, kThreads, 0, (hipStream_t)stream>>>(*w, action, embedding, n, reward, discount,
-                                                                         prior_logits, value, next_embedding);
+  if (ring_scalar_base())
+    k_recurrent<true><<<(n + kRows - 1) / kRows, kThreads, 0, (hipStream_t)stream>>>(
+        *w, action, embedding, n, reward, discount, prior_logits, value, next_embedding);
+  else
+    k_recurrent<false><<<(n + kRows - 1) / kRows, kThreads, 0, (hipStream_t)stream>>>(
+        *w, action, embedding, n, reward, discount, prior_logits, value, next_embedding);
   return muz_last_launch_error();
 }
 

@@ -249,13 +249,69 @@ __device__ __forceinline__ P tree_ld(const P* p) {
 #define MUZ_ACC_CHAINS 1
 #endif
 
-template <int NT, bool AG>
+// Weight addressing of a wave's packed group [kb][lane][tile] (template flag SB of everything below that streams
+// weights; MUZ_RING_ADDR, read per launch, chooses it for k_gumbel_search, k_root_dense and k_recurrent).
+//  SB = true   the group's base is wave-uniform, so it is carried in a scalar register pair (wave_uniform) and the
+//              lane's part is ONE 32-bit byte offset, lane * NT * 16, constant for the layer: a load is
+//              global_load_dwordx4 v, v_off, s[base:base+1] offset:imm, k-block after k-block, and the base advances
+//              on the scalar unit;
+//  SB = false  the form before: a 64-bit address per lane, rebuilt on the vector unit for every k-block.
+// Same loads of the same bytes into the same MFMAs in the same order: the results are bit for bit the same
+// (tests/test_gpu_ring_addressing.py).
+template <class T>
+__device__ __forceinline__ const AS1 T* wave_uniform(const AS1 T* p) {
+  const unsigned long long u = reinterpret_cast<unsigned long long>(p);
+  const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)u);
+  const unsigned hi = __builtin_amdgcn_readfirstlane((unsigned)(u >> 32));
+  return reinterpret_cast<const AS1 T*>(((unsigned long long)hi << 32) | lo);
+}
+// base + bytes, formed on the scalar unit and opaque from there on: left visible, the sum is reassociated into
+// (base + lane offset) + bytes, a 64-bit vector add per load again
+template <class T>
+__device__ __forceinline__ const AS1 T* scalar_advance(const AS1 T* base, size_t bytes) {
+  const AS1 char* p = reinterpret_cast<const AS1 char*>(base) + bytes;
+  asm("" : "+s"(p));
+  return reinterpret_cast<const AS1 T*>(p);
+}
+// f32x4 number `i` (compile-time after unrolling: the instruction's immediate) past base + this lane's byte offset
+// The lane's offset, opaque at the point of use: its zero extension then stays beside the loads, where instruction
+// selection folds it into the scalar-base form; hoisted out of the block it is a 64-bit vector add per load again.
+__device__ __forceinline__ unsigned lane_offset(unsigned voff) {
+  asm("" : "+v"(voff));
+  return voff;
+}
+__device__ __forceinline__ f32x4 ldw_sb(const AS1 char* base, unsigned voff, int i) {
+  return *reinterpret_cast<const AS1 f32x4*>(base + voff + (size_t)i * 16);
+}
+
+#ifdef MUZ_EXPT_NOLOAD   // timing experiment only (wrong results): no weight stream inside the loop
+constexpr bool kRingLoads = false;
+#else
+constexpr bool kRingLoads = true;
+#endif
+// (LOADS = false: the timing experiment again, as a template argument for profiles/loop_bench.hip)
+template <int NT, bool AG, bool SB = false, bool LOADS = kRingLoads>
 __device__ __forceinline__ void mfma_ring_impl(const float* __restrict__ Wg, int KB, const float* A, int lda,
                                                f32x4 (&acc)[NT], f32x4 (&b0)[NT], f32x4 (&b1)[NT]) {
   const int lane = tid() & 63;
   const int r = lane & 15, g = lane >> 4;
-  const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(Wg)) + lane * NT;
   const int wstep = 64 * NT;   // f32x4 per k-block
+  const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(Wg)) + lane * NT;
+  const AS1 char* sb = nullptr;
+  const unsigned voff = (unsigned)lane * (NT * 16);
+  if constexpr (SB) sb = wave_uniform(gp(reinterpret_cast<const char*>(Wg)));
+  // k-block kb's NT float4 of this lane
+  auto ldw = [&](int kb, f32x4 (&dst)[NT]) {
+    if constexpr (SB) {
+      const AS1 char* skb = scalar_advance(sb, (size_t)kb * (wstep * 16));
+      const unsigned vo = lane_offset(voff);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) dst[t] = ldw_sb(skb, vo, t);
+    } else {
+#pragma unroll
+      for (int t = 0; t < NT; ++t) dst[t] = wp[kb * wstep + t];
+    }
+  };
   const float* ap = A + r * lda + 4 * g;
   auto lda4 = [&](int kb) -> f32x4 {
     if constexpr (AG) return *gp(reinterpret_cast<const f32x4*>(ap + kb * 16));
@@ -269,12 +325,9 @@ __device__ __forceinline__ void mfma_ring_impl(const float* __restrict__ Wg, int
   // step kb: issue k-block kb+D into `nxt` (the buffer consumed at step kb-1), read A of kb+1 from LDS,
   // multiply `cur` (= kb) with A of kb
   auto step = [&](int kb, const f32x4 (&cur)[NT], f32x4 (&nxt)[NT], const f32x4& acur, f32x4& anxt) {
-#ifndef MUZ_EXPT_NOLOAD   // timing experiment only (wrong results): no weight stream inside the loop
-    if (kb + D < KB) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) nxt[t] = wp[(kb + D) * wstep + t];
+    if constexpr (LOADS) {
+      if (kb + D < KB) ldw(kb + D, nxt);
     }
-#endif
     // Pin the issue point: without this the machine scheduler sinks each weight load next to its
     // first MFMA (one step of cover instead of D) once the loop is fully unrolled.
     __builtin_amdgcn_sched_barrier(0);
@@ -301,10 +354,7 @@ __device__ __forceinline__ void mfma_ring_impl(const float* __restrict__ Wg, int
     if (kb + 1 < KB) step(kb + 1, b1, b0, a1, a0);
   } else {
     f32x4 b2[NT], b3[NT];
-    if (KB > 2) {
-#pragma unroll
-      for (int t = 0; t < NT; ++t) b2[t] = wp[2 * wstep + t];
-    }
+    if (KB > 2) ldw(2, b2);
     for (; kb + 4 <= KB; kb += 4) {
       step(kb, b0, b3, a0, a1);
       step(kb + 1, b1, b0, a1, a0);
@@ -321,52 +371,80 @@ __device__ __forceinline__ void mfma_ring_impl(const float* __restrict__ Wg, int
   }
 }
 
-template <int NT>
+template <int NT, bool SB = true>
 __device__ __forceinline__ void mfma_ring(const float* __restrict__ Wg, int KB, const float* A, int lda,
                                           f32x4 (&acc)[NT], f32x4 (&b0)[NT], f32x4 (&b1)[NT], bool a_global) {
   if (a_global)
-    mfma_ring_impl<NT, true>(Wg, KB, A, lda, acc, b0, b1);
+    mfma_ring_impl<NT, true, SB>(Wg, KB, A, lda, acc, b0, b1);
   else
-    mfma_ring_impl<NT, false>(Wg, KB, A, lda, acc, b0, b1);
+    mfma_ring_impl<NT, false, SB>(Wg, KB, A, lda, acc, b0, b1);
 }
 
-template <int NT>
+template <int NT, bool SB = true>
 __device__ __forceinline__ void mfma_rows16(const float* __restrict__ Wg, int KB, const float* A, int lda,
                                             f32x4 (&acc)[NT]) {
   const int lane = tid() & 63;
-  const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(Wg)) + lane * NT;
   f32x4 b0[NT], b1[NT];
+  if constexpr (SB) {
+    const AS1 char* sb = wave_uniform(gp(reinterpret_cast<const char*>(Wg)));
+    const unsigned voff = lane_offset((unsigned)lane * (NT * 16));
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    b0[t] = wp[t];
-    b1[t] = KB > 1 ? wp[64 * NT + t] : b0[t];
+    for (int t = 0; t < NT; ++t) {
+      b0[t] = ldw_sb(sb, voff, t);
+      b1[t] = KB > 1 ? ldw_sb(sb, voff, 64 * NT + t) : b0[t];
+    }
+  } else {
+    const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(Wg)) + lane * NT;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      b0[t] = wp[t];
+      b1[t] = KB > 1 ? wp[64 * NT + t] : b0[t];
+    }
   }
-  mfma_ring_impl<NT, false>(Wg, KB, A, lda, acc, b0, b1);
+  mfma_ring_impl<NT, false, SB>(Wg, KB, A, lda, acc, b0, b1);
 }
 
 // ---- cross-layer weight prefetch ----------------------------------------------------------------
 // Every dense layer issues the first two k-blocks of the NEXT layer's weights for this wave before its
 // epilogue, so the loads fly across the epilogue, the barrier and the LayerNorm pass in between.
+// The buffer's type carries the weight addressing (SB above) through every function that takes it: a kernel
+// declares PfT<SB> and the layers below follow; Pf is the scalar-base form.
 constexpr int kPfMax = NT384;
-struct Pf {
+template <bool SB>
+struct PfT {
+  static constexpr bool kScalarBase = SB;
   f32x4 v0[kPfMax], v1[kPfMax];
 };
+using Pf = PfT<true>;
 
+// SB: the wave's index as a scalar, so the whole sum is formed on the scalar unit
+template <bool SB = false>
 __device__ __forceinline__ const float* wave_group(const AS4 muz_dense& L, int KB, int NT) {
-  return L.w + (size_t)(tid() >> 6) * KB * 64 * NT * 4;
+  if constexpr (SB) return L.w + (size_t)__builtin_amdgcn_readfirstlane(tid() >> 6) * KB * 64 * NT * 4;
+  else return L.w + (size_t)(tid() >> 6) * KB * 64 * NT * 4;
 }
 
-template <int NT>
-__device__ __forceinline__ void pf_issue(Pf& pf, const AS4 muz_dense* L, int K, int N) {
+template <int NT, class PF>
+__device__ __forceinline__ void pf_issue(PF& pf, const AS4 muz_dense* L, int K, int N) {
   static_assert(NT <= kPfMax, "prefetch buffer too small");
   if (!L) return;
   const int KB = (K + 15) >> 4;
   if ((tid() >> 6) * NT * 16 >= N) return;
-  const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(wave_group(*L, KB, NT))) + (tid() & 63) * NT;
+  if constexpr (PF::kScalarBase) {
+    const AS1 char* sb = gp(reinterpret_cast<const char*>(wave_group<true>(*L, KB, NT)));
+    const unsigned voff = lane_offset((tid() & 63) * (NT * 16));
 #pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    pf.v0[t] = wp[t];
-    if (KB > 1) pf.v1[t] = wp[64 * NT + t];
+    for (int t = 0; t < NT; ++t) {
+      pf.v0[t] = ldw_sb(sb, voff, t);
+      if (KB > 1) pf.v1[t] = ldw_sb(sb, voff, 64 * NT + t);
+    }
+  } else {
+    const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(wave_group(*L, KB, NT))) + (tid() & 63) * NT;
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+      pf.v0[t] = wp[t];
+      if (KB > 1) pf.v1[t] = wp[64 * NT + t];
+    }
   }
 }
 
@@ -374,17 +452,26 @@ __device__ __forceinline__ void pf_issue(Pf& pf, const AS4 muz_dense* L, int K, 
 // `pf` holds this layer's first k-blocks on entry and the next layer's (Ln: K=Kn, N=Nn, NTN tiles)
 // on exit.  A may live in LDS or global memory.  Caller synchronises before/after.
 // split-K prefetch of a <= 32-column layer (logits16_splitk): wave w takes k-block w of column tiles 0 and 1
-__device__ __forceinline__ void pf_issue_splitk(Pf& pf, const AS4 muz_dense* L, int K) {
+template <class PF>
+__device__ __forceinline__ void pf_issue_splitk(PF& pf, const AS4 muz_dense* L, int K) {
   const int KB = (K + 15) >> 4, w = tid() >> 6;
   if (w >= KB) return;
-  const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(L->w)) + (tid() & 63);
-  pf.v0[0] = wp[(0 * KB + w) * 64];   // packed [group][kb][lane][t = 0][4], groups = 16-column tiles
-  pf.v1[0] = wp[(1 * KB + w) * 64];
+  // packed [group][kb][lane][t = 0][4], groups = 16-column tiles
+  if constexpr (PF::kScalarBase) {
+    const AS1 char* sb = gp(reinterpret_cast<const char*>(L->w)) + (size_t)__builtin_amdgcn_readfirstlane(w) * 1024;
+    const unsigned voff = lane_offset((tid() & 63) * 16);
+    pf.v0[0] = ldw_sb(sb, voff, 0);
+    pf.v1[0] = ldw_sb(sb, voff, KB * 64);
+  } else {
+    const AS1 f32x4* wp = gp(reinterpret_cast<const f32x4*>(L->w)) + (tid() & 63);
+    pf.v0[0] = wp[(0 * KB + w) * 64];
+    pf.v1[0] = wp[(1 * KB + w) * 64];
+  }
 }
 
-template <int NT, int NTN>
+template <int NT, int NTN, class PF>
 __device__ __forceinline__ void dense16(const AS4 muz_dense& L, int K, int N, const float* A, int lda, float* out,
-                                        int ldo, Pf& pf, const AS4 muz_dense* Ln, int Kn, int Nn,
+                                        int ldo, PF& pf, const AS4 muz_dense* Ln, int Kn, int Nn,
                                         bool a_global = false, bool next_splitk = false) {
   const int lane = tid() & 63, wv = tid() >> 6;
   const int KB = (K + 15) >> 4;
@@ -409,7 +496,7 @@ __device__ __forceinline__ void dense16(const AS4 muz_dense& L, int K, int N, co
     b1[t] = pf.v1[t];
   }
   ST(ST_DENTRY);
-  mfma_ring<NT>(wave_group(L, KB, NT), KB, A, lda, acc, b0, b1, a_global);
+  mfma_ring<NT, PF::kScalarBase>(wave_group<PF::kScalarBase>(L, KB, NT), KB, A, lda, acc, b0, b1, a_global);
   ST(ST_MFMA);
   pf_next();
   // The MFMA computes out^T (weights as the A operand), so lane (r, g) holds 4 CONSECUTIVE output
@@ -665,8 +752,8 @@ __device__ __forceinline__ void relu16(float* buf, int ld, int col0, int n) {
 // k-block w of both 16-column tiles (8 MFMAs, operands from pf_issue_splitk) and leaves its partial products in
 // part[w][16][32]; logits16_splitk_sum adds the K / 16 partials and the bias per (row, column) after the next
 // barrier.  The column split kept 6 of the 8 waves idle behind a 32-MFMA chain on two of them.
-template <int NTN>
-__device__ __forceinline__ void logits16_splitk(int K, const float* A, int lda, float* part, Pf& pf,
+template <int NTN, class PF>
+__device__ __forceinline__ void logits16_splitk(int K, const float* A, int lda, float* part, PF& pf,
                                                 const AS4 muz_dense* Ln, int Kn, int Nn) {
   const int lane = tid() & 63, w = tid() >> 6;
   const int KB = (K + 15) >> 4;
@@ -768,9 +855,9 @@ __device__ __forceinline__ LnE<NT> lne_load(const AS4 muz_ln& P) {
   return p;
 }
 
-template <int NT, int NTN, int MODE>
+template <int NT, int NTN, int MODE, class PF>
 __device__ __forceinline__ void dense_ln16(const AS4 muz_dense& L, int K, const float* A, int lda, float* out, int ldo,
-                                           Pf& pf, const AS4 muz_dense* Ln, int Kn, int Nn, const LnE<NT>& lp,
+                                           PF& pf, const AS4 muz_dense* Ln, int Kn, int Nn, const LnE<NT>& lp,
                                            float* part) {
   static_assert(NT * 16 * kWaves == LAT, "dense_ln16: the waves' columns cover exactly the 256 outputs");
   const int lane = tid() & 63, wv = tid() >> 6;
@@ -787,7 +874,7 @@ __device__ __forceinline__ void dense_ln16(const AS4 muz_dense& L, int K, const 
     b1[t] = pf.v1[t];
   }
   ST(ST_DENTRY);
-  mfma_ring<NT>(wave_group(L, KB, NT), KB, A, lda, acc, b0, b1, false);
+  mfma_ring<NT, PF::kScalarBase>(wave_group<PF::kScalarBase>(L, KB, NT), KB, A, lda, acc, b0, b1, false);
   ST(ST_MFMA);
   pf_issue<NTN>(pf, Ln, Kn, Nn);
   float s = 0.f, s2 = 0.f;
@@ -850,8 +937,8 @@ __device__ __forceinline__ void dense_ln16(const AS4 muz_dense& L, int K, const 
 
 // ResBlock (muzero_deterministic_madn.py:12-24): X <- relu(X + LN1(D1(relu(LN0(D0(X))))))
 // pf: rb.d0 on entry, (Ln: Kn x Nn, NTN tiles) on exit.  `part`: the arena's LayerNorm partials (MUZ_LN_EPILOGUE).
-template <int NTN>
-__device__ __forceinline__ void resblock16(const AS4 muz_resblock& R, float* X, float* T, float* U, Pf& pf,
+template <int NTN, class PF>
+__device__ __forceinline__ void resblock16(const AS4 muz_resblock& R, float* X, float* T, float* U, PF& pf,
                                            const AS4 muz_dense* Ln, int Kn, int Nn, float* part) {
   if constexpr (MUZ_LN_EPILOGUE != 0) {
     const LnE<NT256> q0 = lne_load<NT256>(R.ln0);
@@ -949,8 +1036,8 @@ __device__ __forceinline__ float softmax3_support(float l0, float l1, float l2) 
 // hidden layer in a.T; P.d2 is then the first logits chunk (NTL tiles per wave, 256 columns), whose first k-blocks
 // pf holds on exit (dog_logits16 runs the chunks).  Ln / Kn / Nn are unused then.
 template <int NTN, bool LN0_DONE = false, bool LATE_HEADS = false, bool SPLITK_LOGITS = false, int NTL = NTA,
-          bool NO_LOGITS = false>
-__device__ __forceinline__ void pred16(const AS4 muz_pred_w& P, int A, const float* lat, const Arena& a, Pf& pf,
+          bool NO_LOGITS = false, class PF = Pf>
+__device__ __forceinline__ void pred16(const AS4 muz_pred_w& P, int A, const float* lat, const Arena& a, PF& pf,
                                        const AS4 muz_dense* Ln, int Kn, int Nn, const AS4 muz_dyn_w* D = nullptr,
                                        int ar = 0) {
   static_assert(!(NO_LOGITS && SPLITK_LOGITS), "split-K logits need the whole logits layer");
@@ -1037,9 +1124,9 @@ __device__ __forceinline__ void pred16(const AS4 muz_pred_w& P, int A, const flo
 // 6 ResBlocks and Dense_4 into a.T -- the head (min-max / LayerNorm) is the caller's.  pf: on exit Ln's first
 // k-blocks.  Ends without a barrier after Dense_4.
 __device__ __forceinline__ bool gr_valid(int g, int n) { return g < n; }
-template <int NTN, bool D0_DONE = false>
+template <int NTN, bool D0_DONE = false, class PF = Pf>
 __device__ __forceinline__ void repr16(const AS4 muz_repr_w& R, const float* __restrict__ obs, int C,
-                                       const float* __restrict__ convout, int g0, int n, const Arena& a, Pf& pf,
+                                       const float* __restrict__ convout, int g0, int n, const Arena& a, PF& pf,
                                        const AS4 muz_dense* Ln, int Kn, int Nn) {
   const int row = trow(), sub = tsub();
   const int gr = g0 + row;
@@ -1126,8 +1213,8 @@ __device__ __forceinline__ DynIn dyn_load(const AS4 muz_dyn_w& D, int A, const A
 // pred16<.., true>, whose first writes (ResBlock_0's Dense_0 into a.T) come after d67 has consumed a.T.
 // LATE_HEADS (with PRED_LN0): stop after the min-max pass, which leaves the new latent in a.L (and a.T is free),
 // and let pred16<.., true, true> run Dense_6 | Dense_7 and the reward / discount heads; ends with a barrier.
-template <int NTN, bool PRED_LN0 = false, bool LATE_HEADS = false>
-__device__ __forceinline__ void dyn16(const AS4 muz_dyn_w& D, int A, const DynIn& in, int ar, const Arena& a, Pf& pf,
+template <int NTN, bool PRED_LN0 = false, bool LATE_HEADS = false, class PF = Pf>
+__device__ __forceinline__ void dyn16(const AS4 muz_dyn_w& D, int A, const DynIn& in, int ar, const Arena& a, PF& pf,
                                       const AS4 muz_dense* Ln, int Kn, int Nn, const AS4 muz_ln* pln0 = nullptr,
                                       AS1 float* emb = nullptr) {
   static_assert(!LATE_HEADS || PRED_LN0, "late heads need the fused Pred4 LayerNorm_0");

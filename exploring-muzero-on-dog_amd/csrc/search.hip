@@ -78,7 +78,8 @@ struct GumbelTree : TreeWs {
 
 // (prior_probs and completed_q, qtransform_completed_by_mix_value's two halves: tree.hpp, shared with k_env_gumbel)
 
-template <int PARTS>
+// SB: the dense layers' weight addressing (nn.hpp; MUZ_RING_ADDR, read per launch, for the default form of PARTS)
+template <int PARTS, bool SB = true>
 __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
     muz_net_w Wt, SearchArgs sa, const float* __restrict__ root_logits, const float* __restrict__ root_value,
     const float* __restrict__ root_emb, const uint32_t* __restrict__ legal, const float* __restrict__ gumbel_in,
@@ -156,7 +157,7 @@ __global__ __launch_bounds__(kThreads, 1) void k_gumbel_search(
   int cv_m0 = 0;
   if constexpr (CV_TAB) asm volatile("" : "+v"(cv_m0));
   st_begin();
-  Pf pf;   // first k-blocks of the next dense layer (crosses the select / expand phases)
+  PfT<SB> pf;   // first k-blocks of the next dense layer (crosses the select / expand phases)
   pf_issue<NT256>(pf, &kernarg0<muz_net_w>()->dyn.d3, LAT, LAT);
 #pragma unroll 1
   for (int sim = 0; sim < sa.S; ++sim) {
@@ -294,8 +295,14 @@ int launch_gumbel_search(const muz_net_w& w, const SearchArgs& sa, const float* 
                                                          game_id, n, n_dev, T, action, weights, value);
       break;
     default:
-      k_gumbel_search<kSelDefault><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal, gumbel,
-                                                             game_id, n, n_dev, T, action, weights, value);
+      if (ring_scalar_base())
+        k_gumbel_search<kSelDefault, true><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal,
+                                                                     gumbel, game_id, n, n_dev, T, action, weights,
+                                                                     value);
+      else
+        k_gumbel_search<kSelDefault, false><<<grid, kThreads, 0, s>>>(w, sa, root_logits, root_value, root_emb, legal,
+                                                                      gumbel, game_id, n, n_dev, T, action, weights,
+                                                                      value);
   }
   return muz_last_launch_error();
 }

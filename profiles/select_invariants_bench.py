@@ -3,6 +3,7 @@ B = 4096, S = 50, D = 25, a randomly initialised net, root states from 40 plies 
 forms interleaved, 3 repetitions of 16 launches each, HIP events, the median of each repetition.
 
     python profiles/select_invariants_bench.py 0,1,2        # MUZ_LIB=... for another build
+    python profiles/select_invariants_bench.py 0,1 MUZ_RING_ADDR   # the same for another per-launch switch
 
 The switch is read per launch, so one process measures every form of one build."""
 import os
@@ -21,6 +22,7 @@ from exploring_muzero_on_dog_amd import mcts as M  # noqa: E402
 from exploring_muzero_on_dog_amd import nets as N  # noqa: E402
 
 forms = sys.argv[1].split(",")
+SWITCH = sys.argv[2] if len(sys.argv) > 2 else "MUZ_SELECT_INVARIANTS"
 dev = torch.device("cuda")
 P = 2
 C = E.num_channels(P)
@@ -49,11 +51,11 @@ bits = bits[pick].contiguous()
 ws = M.SearchWorkspace(B, S, dev)
 lg, v, e = N.root_inference_fn(net, obs, ws.scratch)
 nl = torch.tensor([bin(int(b) & 0xFFFFFF).count("1") for b in bits.cpu()], dtype=torch.float32)
-print(f"lib {os.environ.get('MUZ_LIB', 'in-tree')}: mean legal actions {float(nl.mean()):.2f}", flush=True)
+print(f"lib {os.environ.get('MUZ_LIB', 'in-tree')}, {SWITCH}: mean legal actions {float(nl.mean()):.2f}", flush=True)
 
 
 def run(form, turn):
-    os.environ["MUZ_SELECT_INVARIANTS"] = form
+    os.environ[SWITCH] = form
     return M.gumbel_muzero_policy(net, lg, v, e, bits, S, D, 1.0, seed=5, turn=turn, workspace=ws)
 
 
