@@ -13,8 +13,9 @@
 //               writes the score to LDS, lanes 0-5 the features to memory where asked
 //   wave 0      the argmax of v(a) over the candidates (temperature 0: of the scores), ties to the smaller action
 //   all waves   the row of scores to memory where asked, zero features for the actions that are not candidates
-// The register step is this file's own dispatch over the shared wv_step_* functions rather than a split of
-// dog_env_step_play_wave into "compute" and "write back": that function is inlined into k_dog_play and k_dog_rollout,
+// The register step (dog_greedy_afterstate, with dog_player_stats in dog_score.hpp, which dog_guided.hip shares) is
+// its own dispatch over the shared wv_step_* functions rather than a split of dog_env_step_play_wave into "compute"
+// and "write back": that function is inlined into k_dog_play and k_dog_rollout,
 // whose register allocation the DOG benchmark measures.  The afterstate needs neither the hands nor the
 // next player (only its board and pins are scored), and a candidate's card is in the hand (it is a bit of the legal
 // mask), so the hand lanes are not loaded at all.
@@ -23,90 +24,13 @@
 #include <climits>
 #include <cmath>
 
-#include "dog_env.hpp"
+#include "dog_score.hpp"
 
 namespace muz {
 
 struct DogGreedyW {
   int w[6];
 };
-
-// What the features need of one player's pins, on the lanes l with (l & 3) == p: progress (calculate_progress of
-// MuZero_DOG/evaluate_agent.py, an exact integer), pins in the goal, pins at home.  `pin` is DogWave's pin lane
-// (lane j < 16: pins[j]); `dist` = 40 / num_players as the reference has it.  Fully unrolled: no array is indexed
-// by a runtime value.
-__device__ __forceinline__ void dog_player_stats(const DetConsts& c, int pin, int lane, int dist, int& prog, int& ngoal,
-                                                 int& nhome) {
-  const int p = lane & 3;
-  const int mt = has(c.flags, R_MUST_TRAVERSE) ? 1 : 0;
-  const int g0 = dgoal0(c, p);
-  int r[4];
-  ngoal = 0;
-  nhome = 0;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) {
-    const int x = __shfl(pin, 4 * p + k);
-    r[k] = x < 0 ? x - 5 : (x < kTrack ? fmodp(x - dist * p, kTrack) - mt : kTrack + (x - g0));
-    ngoal += x >= kTrack ? 1 : 0;
-    nhome += x < 0 ? 1 : 0;
-  }
-  auto cswap = [](int& a, int& b) {
-    const int lo = a < b ? a : b, hi = a < b ? b : a;
-    a = lo;
-    b = hi;
-  };
-  cswap(r[0], r[1]);
-  cswap(r[2], r[3]);
-  cswap(r[0], r[2]);
-  cswap(r[1], r[3]);
-  cswap(r[1], r[2]);
-  // greedy matching of the sorted pins (rows) to the cells 40..43 (columns): four times the smallest distance of the
-  // rows and columns left, the first (row, column) in row-major order on ties
-  unsigned rows = 0u, cols = 0u;
-  prog = 0;
-#pragma unroll
-  for (int round = 0; round < 4; ++round) {
-    int best = INT_MAX, bi = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int d = abs(r[i] - (kTrack + j));
-        const bool open = !((rows >> i) & 1u) && !((cols >> j) & 1u);
-        if (open && d < best) {
-          best = d;
-          bi = i * 4 + j;
-        }
-      }
-    prog += best;
-    rows |= 1u << (bi >> 2);
-    cols |= 1u << (bi & 3);
-  }
-}
-
-// the transition of a legal play-phase action on the wave's registers (dog_env_step_play_wave without the hand, the
-// next player and the write-back); the root is not finished
-__device__ __forceinline__ void dog_greedy_afterstate(const DetConsts& c, DogWave& W, int scp, int action) {
-  const int cp = (has(c.flags, R_TEAMS) && DogWave::player_done(c, W.occupied(), scp)) ? (scp + 2) % 4 : scp;
-  const int act = action % kDogBase;
-  int reward = 0, done = 0;
-  if (act < kDogSwaps) {
-    wv_step_swap(c, W, 0, cp, act / kCells, act % kCells, reward, done);
-  } else if (act < kDogNormalBase) {
-    int d[4];
-#pragma unroll
-    for (int k = 0; k < 4; ++k) d[k] = c_dists7[act - kDogSwaps][k];
-    wv_step_hot7(c, W, 0, cp, d, reward, done);
-  } else if (act < kDogNegBase) {
-    const int na = act - kDogNormalBase;
-    int mv = na % 12 + 1;
-    mv += mv >= 7 ? 1 : 0;
-    wv_step_normal(c, W, 0, cp, na / 12, mv, reward, done);
-  } else {
-    wv_capture_move(c, W, 0, cp, act - kDogNegBase, fmodp(W.pins(cp * 4 + act - kDogNegBase) - 4, kTrack), reward,
-                    done);
-  }
-}
 
 __global__ __launch_bounds__(kDogBlockThreads) void k_dog_greedy(DetConsts c, DogGreedyW wt, float temperature,
                                                                  unsigned long long seed, int turn, muz_dog_soa st,

@@ -16,85 +16,13 @@
 //                                the best one's action and value
 // The turn loop is written out here rather than shared with k_dog_play as one function: k_dog_play's loop also resets,
 // records and counts episodes, and its register allocation is what the DOG benchmark measures.
+// The streams, the determinization and the item lookup are in dog_rollout.hpp, shared with dog_guided.hip, whose search
+// is this one with its own rollout kernel: dog_rollout_check / dog_rollout_launch below take the phase's launch as a
+// function.
 #undef MUZ_DOG_STAMPS   // the stamps build instruments k_dog_play only (its counters live in env_dog.hip)
-#include "dog_env.hpp"
+#include "dog_rollout.hpp"
 
 namespace muz {
-
-// Streams of a rollout (include/muz.h, DOG rollout agent).  Rollout j of the root (seed, game, turn) has its own
-// 64-bit seed; the rollout's deals and random actions are the engine's own streams under that seed (dog_deal,
-// random_action_uniform with the rollout's turn counter), its determinization draws the stream below.  Nothing is keyed
-// by the root action: the candidates of a phase share their random numbers.
-constexpr unsigned long long kDogRolloutStream = 0xD06B0110A7ull;
-constexpr unsigned long long kDogRolloutMul = 0xC2B2AE3D27D4EB4Full;
-constexpr unsigned long long kDogDetStream = 0xD06DE7E5ull;
-constexpr unsigned long long kDogDetMul = 0x9FB21C651E98DF25ull;
-
-__device__ __forceinline__ unsigned long long dog_rollout_seed(unsigned long long seed, int gid, int turn, int j) {
-  return mix64(game_key(seed ^ kDogRolloutStream, gid, turn) ^ (unsigned long long)(j + 1) * kDogRolloutMul);
-}
-__device__ __forceinline__ float dog_det_uniform(unsigned long long rseed, int i) {
-  return u24(mix64(rseed ^ kDogDetStream ^ (unsigned long long)(i + 1) * kDogDetMul));
-}
-
-// draw i of a determinization: the floor(u tot)-th card of the multiset in s.deck (tot > 0 cards), taken out of it
-__device__ __forceinline__ int dog_det_draw(DogG& s, unsigned long long rseed, int i, int tot) {
-  int k = (int)(dog_det_uniform(rseed, i) * (float)tot);
-  k = k >= tot ? tot - 1 : k;
-  int card = kDogCards - 1, acc = 0;
-  bool found = false;
-  for (int d = 0; d < kDogCards; ++d) {
-    const int n = s.deck[d];
-    if (!found && k < acc + n) {
-      card = d;
-      found = true;
-    }
-    acc += n;
-  }
-  s.deck[card] = (int8_t)(s.deck[card] - 1);
-  return card;
-}
-
-// Determinization of the game in LDS (one lane).  The observers are the current player m and m' = dog_sub(m); the
-// hidden multiset H is the deck plus every other seat's hand plus every other seat's swap choice (a card that left
-// the hand in the swap phase and has not been handed over yet); it is gathered into s.deck.  Then, for the hidden
-// seats q ascending: as many cards as q's hand held, then q's swap choice if it had one, each the floor(u |H|)-th card
-// of H in card order, without replacement.  What is left of H is the deck.  Nothing else changes.
-__device__ void dog_determinize(const DetConsts& c, DogG& s, unsigned long long rseed) {
-  const int m = s.cp, mp = dog_sub(c, s);
-  unsigned cnt = 0u, had = 0u;   // byte q: cards in q's hand; bit q: q has a swap choice
-  int tot = 0;
-  for (int k = 0; k < kDogCards; ++k) tot += s.deck[k];
-  for (int q = 0; q < c.P; ++q) {
-    if (q == m || q == mp) continue;
-    int n = 0;
-    for (int k = 0; k < kDogCards; ++k) {
-      const int h = s.hands[q][k];
-      n += h;
-      s.deck[k] = (int8_t)(s.deck[k] + h);
-      s.hands[q][k] = 0;
-    }
-    n = n < 0 ? 0 : (n > 255 ? 255 : n);
-    const int sc = s.swap_choices[q];
-    if (sc >= 0 && sc < kDogCards) {
-      s.deck[sc] = (int8_t)(s.deck[sc] + 1);
-      had |= 1u << q;
-      ++tot;
-    }
-    cnt |= (unsigned)n << (8 * q);
-    tot += n;
-  }
-  int i = 0;
-  for (int q = 0; q < c.P; ++q) {
-    if (q == m || q == mp) continue;
-    const int n = (int)((cnt >> (8 * q)) & 0xFFu);
-    for (int d = 0; d < n && tot > 0; ++d) {
-      const int card = dog_det_draw(s, rseed, i++, tot--);
-      s.hands[q][card] = (int8_t)(s.hands[q][card] + 1);
-    }
-    if (((had >> q) & 1u) && tot > 0) s.swap_choices[q] = (int8_t)dog_det_draw(s, rseed, i++, tot--);
-  }
-}
 
 // ---- the candidate lists -----------------------------------------------------------------------------------------
 // One workgroup per game, as k_dog_legal.  cand[g][0 .. ncand[g]) = the legal actions ascending; a finished game has
@@ -161,24 +89,6 @@ __global__ __launch_bounds__(kPlanThreads) void k_dog_rollout_plan(const int32_t
 }
 
 // ---- the rollouts ------------------------------------------------------------------------------------------------
-struct DogRolloutArgs {
-  DetConsts c;
-  muz_dog_soa st;            // the roots (read only)
-  const int32_t* game_id;    // null: the game's index
-  unsigned long long seed;
-  int turn, phase, R, steps, determinize;
-  const int32_t* cand;       // [n][806]
-  const int32_t* off;        // [n + 1] (k_dog_rollout_plan)
-  int32_t* wins;             // [n][806]
-  uint32_t* turns;           // [n]
-  int n;
-};
-
-struct DogItem {   // the workgroup's item, in LDS (wave-uniform values re-read where they are used, not held live)
-  int g, a0, gid, side;
-  unsigned long long rseed;
-};
-
 // Item i of a phase: candidate slot i / R of the phase's concatenated lists, rollout i % R of the phase.  The
 // workgroup copies the root into LDS, determinizes it, applies the candidate (turn -1) and plays k_dog_play's turn
 // until the game ends or `steps` turns are played.  Barriers: every wave takes the same ones.  The only exit from the
@@ -213,20 +123,7 @@ __global__ __launch_bounds__(kDogPlayThreads) __attribute__((amdgpu_waves_per_eu
 #endif
   const int items = A().off[A().n] * A().R;
   for (int item = blockIdx.x; item < items; item += gridDim.x) {
-    if (tid == 0) {   // the item's game: the last g with off[g] <= slot (games that do not search have empty ranges)
-      const DogRolloutArgs& P = A();
-      const int slot = item / P.R;
-      int lo = 0, hi = P.n;   // invariant: off[lo] <= slot < off[hi]
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (P.off[mid] <= slot) lo = mid; else hi = mid;
-      }
-      const int gid = P.game_id ? P.game_id[lo] : lo;
-      it.g = lo;
-      it.a0 = P.cand[(size_t)lo * kDogActions + (slot - P.off[lo])];
-      it.gid = gid;
-      it.rseed = dog_rollout_seed(P.seed, gid, P.turn, P.phase * P.R + item % P.R);
-    }
+    if (tid == 0) dog_rollout_item(A(), item, it);
     __syncthreads();   // (also: every wave is done with the previous item's LDS state)
     dog_load<PlaySync>(A().c, A().st, it.g, s, tid);
     if (tid == 0) {
@@ -309,40 +206,36 @@ __global__ __launch_bounds__(kRankThreads) void k_dog_rollout_rank(int32_t* cand
   if (tid == 0) ncand[g] = keep;
 }
 
-constexpr int kRolloutGrid = 2048;   // k_dog_rollout's fixed grid
 static inline int64_t up256(int64_t x) { return (x + 255) / 256 * 256; }
 
-}  // namespace muz
-
-using namespace muz;
-
-extern "C" {
-
-// wins, visits and the candidate lists [n][806] int32, then the candidate counts [n], the rollout turns [n] and the
-// item offsets [n + 1], each block rounded up to 256 bytes
-int64_t muz_dog_rollout_bytes(int32_t n) {
-  if (n < 0) return -1;
-  const int64_t rows = up256((int64_t)n * kDogActions * 4);
-  return 3 * rows + 2 * up256((int64_t)n * 4) + up256(((int64_t)n + 1) * 4);
+static void dog_rollout_phase(unsigned grid, hipStream_t s, const DogRolloutArgs& args, const void*) {
+  k_dog_rollout<<<grid, kDogPlayThreads, 0, s>>>(args);
 }
 
-int muz_dog_rollout_search(const muz_rules* rules, const muz_dog_rollout_cfg* cfg, muz_dog_soa st,
-                           const int32_t* game_id, int32_t* action, float* value, int32_t* visits, int32_t* wins,
-                           uint32_t* rollout_turns, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+int dog_rollout_check(const muz_rules* rules, const muz_dog_rollout_cfg* cfg, const muz_dog_soa& st,
+                      const int32_t* action, const float* value, int32_t n, const void* ws, int64_t ws_bytes,
+                      DetConsts* c, bool* go) {
+  *go = false;
   MUZ_HOST_CHECK(rules && cfg && n >= 0 && st.stride >= n);
   MUZ_HOST_CHECK(cfg->rollouts >= 1 && cfg->rollouts <= 64 && cfg->max_phases >= 1 && cfg->max_phases <= 10 &&
                  cfg->rollout_steps >= 1 && cfg->rollout_steps <= 1000);
   // the item index of a phase (at most n * 806 * R, advanced by the grid's stride) and the prefix sums of the
   // candidate counts are int32
   MUZ_HOST_CHECK((int64_t)n * kDogActions * cfg->rollouts <= (int64_t)INT32_MAX - kRolloutGrid);
-  DetConsts c;
-  int rc = dog_consts(rules, &c);
+  int rc = dog_consts(rules, c);
   if (rc) return rc;
   if (n == 0) return MUZ_OK;
   MUZ_HOST_CHECK(action && value && ws && ((uintptr_t)ws & 15u) == 0 && ws_bytes >= muz_dog_rollout_bytes(n));
   MUZ_HOST_CHECK(st.board && st.pins && st.deck && st.hands && st.swap_choices && st.current_player &&
                  st.round_starter && st.phase && st.hand_size && st.reward && st.done && st.deal);
   if ((rc = dog_tables_ready())) return rc;
+  *go = true;
+  return MUZ_OK;
+}
+
+int dog_rollout_launch(const DetConsts& c, const muz_dog_rollout_cfg* cfg, muz_dog_soa st, const int32_t* game_id,
+                       int32_t* action, float* value, int32_t* visits, int32_t* wins, uint32_t* rollout_turns,
+                       int32_t n, void* ws, void* stream, DogRolloutPhase phase, const void* extra) {
   char* p = (char*)ws;
   const int64_t rows = up256((int64_t)n * kDogActions * 4);
   int32_t* w_wins = (int32_t*)p;
@@ -361,13 +254,36 @@ int muz_dog_rollout_search(const muz_rules* rules, const muz_dog_rollout_cfg* cf
   const unsigned grid = (unsigned)(most < kRolloutGrid ? most : kRolloutGrid);
   for (int ph = 0; ph < cfg->max_phases; ++ph) {
     k_dog_rollout_plan<<<1, kPlanThreads, 0, s>>>(ncand, off, n);
-    k_dog_rollout<<<grid, kDogPlayThreads, 0, s>>>(DogRolloutArgs{c, st, game_id, cfg->seed, cfg->turn, ph,
-                                                                  cfg->rollouts, cfg->rollout_steps,
-                                                                  cfg->determinize ? 1 : 0, cand, off, wins,
-                                                                  rollout_turns, n});
+    phase(grid, s, DogRolloutArgs{c, st, game_id, cfg->seed, cfg->turn, ph, cfg->rollouts, cfg->rollout_steps,
+                                  cfg->determinize ? 1 : 0, cand, off, wins, rollout_turns, n}, extra);
     k_dog_rollout_rank<<<n, kRankThreads, 0, s>>>(cand, ncand, wins, visits, action, value, cfg->rollouts, n);
   }
   return muz_last_launch_error();
+}
+
+}  // namespace muz
+
+using namespace muz;
+
+extern "C" {
+
+// wins, visits and the candidate lists [n][806] int32, then the candidate counts [n], the rollout turns [n] and the
+// item offsets [n + 1], each block rounded up to 256 bytes
+int64_t muz_dog_rollout_bytes(int32_t n) {
+  if (n < 0) return -1;
+  const int64_t rows = up256((int64_t)n * kDogActions * 4);
+  return 3 * rows + 2 * up256((int64_t)n * 4) + up256(((int64_t)n + 1) * 4);
+}
+
+int muz_dog_rollout_search(const muz_rules* rules, const muz_dog_rollout_cfg* cfg, muz_dog_soa st,
+                           const int32_t* game_id, int32_t* action, float* value, int32_t* visits, int32_t* wins,
+                           uint32_t* rollout_turns, int32_t n, void* ws, int64_t ws_bytes, void* stream) {
+  DetConsts c;
+  bool go = false;
+  const int rc = dog_rollout_check(rules, cfg, st, action, value, n, ws, ws_bytes, &c, &go);
+  if (rc || !go) return rc;
+  return dog_rollout_launch(c, cfg, st, game_id, action, value, visits, wins, rollout_turns, n, ws, stream,
+                            dog_rollout_phase, nullptr);
 }
 
 }  // extern "C"

@@ -18,7 +18,9 @@ reference's ``encode_board`` is a stub (dog.py:1264-1272), so there is no DOG ob
 ``rollout_policy`` is the network-free rollout agent (csrc/dog_rollout.hip): the reference has no DOG agent that
 runs, so it is this engine's own and parity-unpinned; ``tests/_dog_rollout.py`` defines it.  ``greedy_policy`` is the
 one-ply greedy agent and ``afterstate_features`` the per-action board features it scores (csrc/dog_greedy.hip), the
-engine's own in the same way; ``tests/_dog_greedy.py`` defines them.
+engine's own in the same way; ``tests/_dog_greedy.py`` defines them.  ``guided_rollout_policy`` is the rollout agent
+whose playout turns pick among the greedy agent's best-scored actions (csrc/dog_guided.hip); ``tests/_dog_guided.py``
+defines it.
 """
 from __future__ import annotations
 
@@ -322,6 +324,60 @@ def greedy_policy(env, *, weights: dict | None = None, temperature: float | None
     action, scores, features = _greedy(env, "greedy_policy", [v[k] for k in GREEDY_FEATURES], t, seed, turn, game_id,
                                        summary, summary)
     return (action, scores, features) if summary else action
+
+
+# ---- the rollout agent with greedy-guided playouts (csrc/dog_guided.hip; include/muz.h, DOG guided rollout agent) -----
+GUIDED_EPSILON = 0.125   # an unmeasured choice, exact in float32 (profiles/dog_guided_bench.log reports other values)
+
+
+def guided_rollout_policy(env, rollouts: int = 4, *, weights: dict | None = None, epsilon: float = GUIDED_EPSILON,
+                          max_phases: int = 10, rollout_steps: int = 300, determinize: bool = True, seed: int,
+                          turn: int, game_id: torch.Tensor | None = None, workspace: RolloutWorkspace | None = None,
+                          summary: bool = False):
+    """``rollout_policy`` with greedy-guided playouts (int32 [B]; -1 for a finished game or one without a legal action):
+    the same root-level search -- candidates, phases, sequential halving, re-drawn hidden cards, streams --, but a
+    playout turn picks uniformly among the actions the greedy agent scores best (``weights``: a dict over
+    GREEDY_FEATURES, missing keys take GREEDY_DEFAULTS, integers in [-32768, 32767]; there is no temperature), and with
+    probability ``epsilon`` (a float32 in [0, 1]) uniformly among all legal actions, as the random playout does.  With
+    ``epsilon`` 1 it is ``rollout_policy``, output for output (muz_dog_guided_rollout_search; the semantics are in
+    include/muz.h, the definition is tests/_dog_guided.py -- the reference has no DOG agent that runs, parity is
+    unpinned).  ``env`` is not changed; ``workspace`` is ``rollout_policy``'s.  With ``summary`` returns (action, value
+    float32 [B], visits int32 [B, 806], wins int32 [B, 806], rollout_turns int32 [B], decided int32 [B]: the rollouts
+    of a game whose outcome was not 0)."""
+    if not isinstance(env, DOGState):
+        raise TypeError(f"guided_rollout_policy searches a DOG state (dog.DOGState), not {type(env).__name__}")
+    unknown = set(weights or {}) - set(GREEDY_FEATURES)
+    if "temperature" in unknown:
+        raise ValueError("guided_rollout_policy has no temperature: a playout turn picks uniformly among the "
+                         "best-scored actions, and epsilon sets the share of uniformly random turns")
+    if unknown:
+        raise ValueError(f"unknown greedy weights {sorted(unknown)} (the features are {GREEDY_FEATURES})")
+    v = dict(GREEDY_DEFAULTS)
+    v.update(weights or {})
+    eps = float(epsilon)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError(f"epsilon is a probability in [0, 1], not {epsilon!r}")
+    B, dev = env.batch, env.board.device
+    if workspace is None:
+        workspace = RolloutWorkspace(B, dev)
+    if workspace.n < B:
+        raise ValueError(f"the workspace holds {workspace.n} games, the state {B}")
+    cfg = _L.MuzDogGuidedCfg(_L.MuzDogRolloutCfg(int(rollouts), int(max_phases), int(rollout_steps),
+                                                 int(bool(determinize)), ctypes_u64(seed), int(turn)),
+                             (ctypes.c_int32 * 6)(*[int(v[k]) for k in GREEDY_FEATURES]), eps)
+    gid = None if game_id is None else game_id.to(device=dev, dtype=torch.int32).reshape(B).contiguous()
+    action = torch.empty((B,), dtype=torch.int32, device=dev)
+    value = torch.empty((B,), dtype=torch.float32, device=dev)
+    visits = wins = turns = decided = None
+    if summary:
+        visits = torch.empty((B, ACTIONS), dtype=torch.int32, device=dev)
+        wins = torch.empty((B, ACTIONS), dtype=torch.int32, device=dev)
+        turns = torch.empty((B,), dtype=torch.int32, device=dev)
+        decided = torch.empty((B,), dtype=torch.int32, device=dev)
+    _call("muz_dog_guided_rollout_search", env.rules, ctypes.byref(cfg), env.soa(), _L.ptr(gid), _L.ptr(action),
+          _L.ptr(value), _L.ptr(visits), _L.ptr(wins), _L.ptr(turns), _L.ptr(decided), B, _L.ptr(workspace.buf),
+          _L.nbytes(workspace.buf), _L.stream_ptr())
+    return (action, value, visits, wins, turns, decided) if summary else action
 
 
 # ---- action <-> move helpers (dog.py:1133-1262), host side ---------------------------------------------

@@ -25,6 +25,8 @@
   'greedy_agent'                DOG's cheap scripted seat (DOG only): every legal action tried once on the real
                                 environment and scored by the board it leads to, dog.greedy_policy over the whole
                                 batch (the reference's rule-based DOG agent cannot run; parity unpinned).
+  'guided_rollout_agent'        the rollout seat with greedy-guided playouts (DOG only): dog.guided_rollout_policy, whose
+                                playout turns pick among the greedy agent's best-scored actions (parity unpinned).
   policy_action                 the random agent (770-775) and the rule-based agent (777-864) as one device
                                 kernel (muz_detmadn_policy_action), sampling by Gumbel-max on the counter RNG.
 
@@ -91,6 +93,14 @@ _NO_GREEDY_DET = ("the greedy agent (dog.greedy_policy) is DOG's, whose referenc
                   "det-MADN's scripted seat is its own 'rule_based_agent'")
 _NO_GREEDY_CLASSIC = ("the greedy agent (dog.greedy_policy) is DOG's, whose reference rule-based agent cannot run: "
                       "classic MADN's scripted seat is its own 'rule_based_agent'")
+# DOG's rollout seat with greedy-guided playouts (dog.guided_rollout_policy); rollouts, rollout_steps and determinize
+# are the rollout seat's, epsilon and the weights come with the evaluation's ``guided`` dict
+GUIDED_ROLLOUT_AGENT = "guided_rollout_agent"
+_NO_GUIDED_DET = ("the guided rollout agent (dog.guided_rollout_policy) is DOG's: det-MADN's network-free seats are "
+                  "'mcts_agent' and 'gumbel_mcts_agent'; its other named seats are 'rule_based_agent' and "
+                  "'random_agent'")
+_NO_GUIDED_CLASSIC = ("the guided rollout agent (dog.guided_rollout_policy) is DOG's: classic MADN's network-free seat "
+                      "is 'stochastic_mcts_agent'; its other named seats are 'rule_based_agent' and 'random_agent'")
 
 # classic MADN, MuZero_Classic_MADN/evaluate_agent_stochastic.py:938-948 (the keys it leaves out take env_reset's
 # defaults: no dice rethrow)
@@ -316,6 +326,7 @@ class _Game:
     GUMBEL_SEAT = None                         # the name of that seat under the Gumbel policy, if the game has one
     ROLLOUT_SEAT = None                        # the name of the game's root-level rollout seat, if it has one
     GREEDY_SEAT = None                         # the name of the game's one-ply greedy scripted seat, if it has one
+    GUIDED_SEAT = None                         # the name of the game's guided rollout seat, if it has one
 
     @classmethod
     def reset(cls, n, sp, seed, device, r):
@@ -339,7 +350,8 @@ class _Game:
 
 class _Det(_Game):
     env, RULES, C = E, RULES, E.num_channels(4)
-    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET, GREEDY_AGENT: _NO_GREEDY_DET}
+    REFUSED = {STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_DET, GREEDY_AGENT: _NO_GREEDY_DET,
+               GUIDED_ROLLOUT_AGENT: _NO_GUIDED_DET}
     ENV_SEAT = MCTS_AGENT
     GUMBEL_SEAT = GUMBEL_MCTS_AGENT
     workspace = staticmethod(M.SearchWorkspace)
@@ -385,7 +397,7 @@ class _Classic(_Game):
     soft lock aware) before the agents move."""
     env, RULES, C = CL, CLASSIC_RULES, CL.num_channels(4)
     REFUSED = {MCTS_AGENT: _NO_ENV_MODEL, ROLLOUT_AGENT: _NO_ROLLOUT_CLASSIC, GUMBEL_MCTS_AGENT: _NO_GUMBEL_CLASSIC,
-               GREEDY_AGENT: _NO_GREEDY_CLASSIC}
+               GREEDY_AGENT: _NO_GREEDY_CLASSIC, GUIDED_ROLLOUT_AGENT: _NO_GUIDED_CLASSIC}
     ENV_SEAT = STOCHASTIC_MCTS_AGENT
     scripted = staticmethod(classic_policy_action)
     env_workspace = staticmethod(ST.ClassicEnvSearchWorkspace)
@@ -436,6 +448,7 @@ class _Dog(_Game):
                MCTS_AGENT: _NO_ENV_MODEL, STOCHASTIC_MCTS_AGENT: _NO_CHANCE_MODEL, GUMBEL_MCTS_AGENT: _NO_GUMBEL_DOG}
     ROLLOUT_SEAT = ROLLOUT_AGENT
     GREEDY_SEAT = GREEDY_AGENT
+    GUIDED_SEAT = GUIDED_ROLLOUT_AGENT
     legal = staticmethod(DOG.legal_mask)
     workspace = staticmethod(MD.SearchWorkspace)
     rollout_workspace = staticmethod(DOG.RolloutWorkspace)
@@ -444,6 +457,14 @@ class _Dog(_Game):
     def rollout_search(sub, gid, seed, turn, rws, rollout):
         """The 'rollout_agent' seat: dog.rollout_policy on the seat's gathered games, keyed by the games' ids."""
         return DOG.rollout_policy(sub, seed=seed, turn=turn, game_id=gid, workspace=rws, **rollout)
+
+    @staticmethod
+    def guided_search(sub, gid, seed, turn, rws, rollout, guided):
+        """The 'guided_rollout_agent' seat: dog.guided_rollout_policy on the seat's gathered games with the rollout
+        seat's keywords and workspace and the parameters ``guided`` (epsilon, weights; None: the defaults), keyed by
+        the games' ids."""
+        return DOG.guided_rollout_policy(sub, seed=seed, turn=turn, game_id=gid, workspace=rws, **rollout,
+                                         **(guided or {}))
 
     @staticmethod
     def reset(n, sp, seed, device, r):   # block sp's deals are keyed by seed + sp
@@ -492,17 +513,18 @@ def _seat(game, a, i, seed, device):
         if a in game.REFUSED:
             raise ValueError(game.REFUSED[a])
         if a not in ("rule_based_agent", "random_agent", game.ENV_SEAT, game.GUMBEL_SEAT, game.ROLLOUT_SEAT,
-                     game.GREEDY_SEAT):
+                     game.GREEDY_SEAT, game.GUIDED_SEAT):
             raise ValueError(f"unknown agent {a!r}")
         return a
     return game.as_net(a, device)
 
 
 def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws=None,
-          rollout_steps=MCTS_ROLLOUT_STEPS, rws=None, rollout=None) -> bool:
+          rollout_steps=MCTS_ROLLOUT_STEPS, rws=None, rollout=None, guided=None) -> bool:
     """One turn of every unfinished game: per game the agent of its current player -- a search on the gathered
     sub-batch of a seat (a network's, the game's environment-search seat's over the environment -- PUCT or, for the
-    game's Gumbel seat, the Gumbel policy --, or the game's rollout seat's with the keywords ``rollout``), or a scripted agent's launch over the batch -- then the game's
+    game's Gumbel seat, the Gumbel policy --, or the game's rollout seat's with the keywords ``rollout``, its guided
+    rollout seat's with ``guided`` besides), or a scripted agent's launch over the batch -- then the game's
     advance.  False, and nothing played, once every game is
     finished."""
     active = env.done == 0
@@ -528,6 +550,10 @@ def _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent,
             idx = sel.nonzero().flatten()
             act[idx] = game.rollout_search(env.take(idx), gid[idx], seed, turn, rws,
                                            ROLLOUT_DEFAULTS if rollout is None else rollout)
+        elif isinstance(a, str) and a == game.GUIDED_SEAT:
+            idx = sel.nonzero().flatten()
+            act[idx] = game.guided_search(env.take(idx), gid[idx], seed, turn, rws,
+                                          ROLLOUT_DEFAULTS if rollout is None else rollout, guided)
         elif isinstance(a, str):
             act = torch.where(sel, game.scripted(env, legal, a, seed, turn, rule_agent, gid), act)
         else:
@@ -551,14 +577,16 @@ def _mcts_workspace(game, seats, n, S, device):
 
 
 def _rollout_workspace(game, seats, n, device):
-    """The workspace of the game's rollout seat, when one of the seats is that agent."""
-    if game.ROLLOUT_SEAT is None or not any(isinstance(x, str) and x == game.ROLLOUT_SEAT for x in seats):
+    """The workspace of the game's rollout seats (one carve serves the rollout and the guided rollout seat), when one of
+    the seats is such an agent."""
+    names = [x for x in (game.ROLLOUT_SEAT, game.GUIDED_SEAT) if x is not None]
+    if not any(isinstance(x, str) and x in names for x in seats):
         return None
     return game.rollout_workspace(n, device)
 
 
 def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_turns, rule_agent, device, skw,
-                report_turns=False, rollout=None) -> dict:
+                report_turns=False, rollout=None, guided=None) -> dict:
     """4 x batch_size games of ``game``, block i started by player i, played to the end or ``max_turns``; the result
     tables, with ``report_turns`` also the number of turns the loop ran."""
     r = dict(game.RULES if rules is None else rules)
@@ -577,7 +605,7 @@ def _four_seats(game, agents, batch_size, S, D, temperature, seed, rules, max_tu
     for turn in range(max_turns):
         turns = turn + 1
         if not _turn(game, env, seats, gid, turn, seed, gen, S, D, temperature, rule_agent, ws, skw, mws, rws=rws,
-                     rollout=rollout):
+                     rollout=rollout, guided=guided):
             break
     return _tables(env, r, batch_size, **({"turns": turns} if report_turns else {}))
 
@@ -687,12 +715,21 @@ def compare_agents_statistically_classic(agent1, agent2, num_games: int = 1000, 
 
 
 # ---- DOG: MuZero_DOG/evaluate_agent.py --------------------------------------------------------------------------
+def _guided_kwargs(guided):
+    """The ``guided`` dict of evaluate_agent_parallel_dog: ``epsilon`` and / or ``weights``, nothing else."""
+    unknown = set(guided or {}) - {"epsilon", "weights"}
+    if unknown:
+        raise ValueError(f"unknown guided rollout parameters {sorted(unknown)} (they are 'epsilon' and 'weights'; "
+                         "rollouts, rollout_steps and determinize are the evaluation's own keywords)")
+    return dict(guided or {})
+
+
 @torch.no_grad()
 def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: int = DOG_SIMULATIONS,
                                 max_depth: int = DOG_DEPTH, temperature: float = DOG_TEMPERATURE, seed: int = 0,
                                 rules: dict | None = None, max_turns: int = 2000, device="cuda", *, rollouts: int = 4,
                                 rollout_steps: int = MCTS_ROLLOUT_STEPS, determinize: bool = True,
-                                greedy: dict | None = None) -> dict:
+                                greedy: dict | None = None, guided: dict | None = None) -> dict:
     """evaluate_agent_parallel (MuZero_DOG/evaluate_agent.py:255-313) with play_n_games_for_eval_jitted /
     play_eval_loop_jitted (315-527): `agents` = the four seats, each the DOG slice's MuZero (a DeviceDogNet or its
     flat params; None = randomly initialised params; run_muzero_mcts at A = 806, S 100, D 50, temperature 0.2),
@@ -701,11 +738,15 @@ def evaluate_agent_parallel_dog(agents, batch_size: int = 20, num_simulations: i
     over dog.GREEDY_DEFAULTS' keys -- None: the defaults; keyed by seed, turn and the game's index) or
     'rollout_agent' (the network-free root-level Monte-Carlo
     search dog.rollout_policy with ``rollouts`` playouts per action and phase of at most ``rollout_steps`` turns, the
-    hidden cards re-drawn when ``determinize``; keyed by seed, turn and the game's index); 4 x batch_size games, block i started by player i, at most
+    hidden cards re-drawn when ``determinize``; keyed by seed, turn and the game's index) or 'guided_rollout_agent' (the
+    same search with greedy-guided playouts, dog.guided_rollout_policy: ``rollouts``, ``rollout_steps`` and
+    ``determinize`` as for 'rollout_agent', ``guided`` a dict with ``epsilon`` and / or ``weights`` -- None: the
+    defaults); 4 x batch_size games, block i started by player i, at most
     2000 turns; a game without a legal action applies no_step.  Every game steps in its own lane each turn (a finished
     game's lane applies no_step, which leaves its pins alone), so a game's deals are keyed by its own index.  Returns
     winners[start][player] and average_progress[start][player] as the reference prints them, and their totals.
     Win-rate parity is unpinned: the reference's DOG networks and inference functions are `pass`."""
     return _four_seats(_Dog, agents, batch_size, num_simulations, max_depth, temperature, seed, rules, max_turns, greedy,
                        device, {}, report_turns=True,
-                       rollout=dict(rollouts=rollouts, rollout_steps=rollout_steps, determinize=determinize))
+                       rollout=dict(rollouts=rollouts, rollout_steps=rollout_steps, determinize=determinize),
+                       guided=_guided_kwargs(guided))

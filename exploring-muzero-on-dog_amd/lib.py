@@ -257,6 +257,10 @@ class MuzDogGreedyCfg(ctypes.Structure):
                 ("turn", ctypes.c_int32)]
 
 
+class MuzDogGuidedCfg(ctypes.Structure):
+    _fields_ = [("rollout", MuzDogRolloutCfg), ("w", ctypes.c_int32 * 6), ("epsilon", ctypes.c_float)]
+
+
 class MuzSearchCfg(ctypes.Structure):
     _fields_ = [("num_simulations", ctypes.c_int32), ("max_depth", ctypes.c_int32),
                 ("max_num_considered", ctypes.c_int32), ("value_scale", ctypes.c_float),
@@ -336,6 +340,9 @@ SIGNATURES = {
                                               vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp, ctypes.c_int64, vp]),
     "muz_dog_greedy_action": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzDogGreedyCfg), MuzDogSoA,
                                              vp, vp, vp, vp, ctypes.c_int32, vp]),
+    "muz_dog_guided_rollout_search": (ctypes.c_int, [ctypes.POINTER(MuzRules), ctypes.POINTER(MuzDogGuidedCfg),
+                                                     MuzDogSoA, vp, vp, vp, vp, vp, vp, vp, ctypes.c_int32, vp,
+                                                     ctypes.c_int64, vp]),
     "muz_classic_reset": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, ctypes.c_int32, vp]),
     "muz_classic_reset_seeded": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, vp, ctypes.c_int32, vp]),
     "muz_classic_set_die": (ctypes.c_int, [ctypes.POINTER(MuzRules), MuzClassicSoA, vp, ctypes.c_int32, vp]),

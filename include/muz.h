@@ -388,6 +388,48 @@ int muz_dog_greedy_action(const muz_rules* rules /*host*/, const muz_dog_greedy_
                           int32_t* action /* [n] */, int32_t* scores /* [n][806], nullable */,
                           int32_t* features /* [n][806][6], nullable */, int32_t n, void* stream);
 
+/* ---- DOG guided rollout agent: the rollout agent with greedy-guided playouts (csrc/dog_guided.hip) -----------------
+ * The random playout of the rollout agent rarely ends a mid-game DOG position within its cap, and a capped playout
+ * scores 0; here the playout turns pick among the actions the greedy agent scores best.  The reference has no DOG agent
+ * that runs, so parity with it is UNPINNED; the definition is tests/_dog_guided.py, which the kernel equals bit for bit
+ * (integer scores and sums; the two float32 operations of a turn are muz_dog_random_action's).
+ * The search is muz_dog_rollout_search with ONE change, the policy of the playout turns t >= 0.  The candidates, the
+ * phases and the halving schedule, the ranking and the value division, the determinization and the deals, the root
+ * action as turn -1, the outcome, rollout_turns and the rollout seed rseed (same stream, same constants) are exactly as
+ * the DOG rollout agent section has them.  The new inputs are w[6], the DOG greedy agent's weights with their meaning
+ * and range, and epsilon, a float32 in [0, 1].
+ *   Playout turn t on the playout's current state e with mover m:
+ *   C = the legal actions of e, ascending.  C empty: no_step, as in the rollout agent.
+ *   scores[a], a in C = the greedy agent's scores of e as muz_dog_greedy_action defines them: the features of the
+ *   afterstate without the deal, ME and OP taken from m's side, a finished team player moving its partner's pins;
+ *   swap-phase actions (792..805) have features 0, so every score of a swap-phase turn is 0.
+ *   The turn EXPLORES iff u_e < epsilon (one float32 compare: epsilon 1 always explores, epsilon 0 never does),
+ *     u_e = U24(mix64(rseed ^ 0xE9B10AE0D6 ^ mix64(game_id << 32 | t))).
+ *   M = C when the turn explores, else the actions of C whose score equals the greatest (in the swap phase: all of C).
+ *   The action is the k-th member of M in ascending action order, k = min(floor(u_t |M|), |M| - 1) in float32, u_t the
+ *   uniform random turn t already draws: muz_dog_random_action's with (rseed, game_id, t).
+ * Ties are broken uniformly, never by the smallest action (the greedy agent's first-argmax rule would always play the
+ * joker copy of a move and hand over card 0).  There is no logf and no temperature.  With epsilon 1 the search is
+ * muz_dog_rollout_search, output for output.  Nothing is keyed by the root action or by the position in the batch. */
+typedef struct muz_dog_guided_cfg {
+  muz_dog_rollout_cfg rollout;
+  int32_t w[6];        /* advance, setback, goal, out, hit, win; each in [-32768, 32767] */
+  float epsilon;       /* in [0, 1]: the share of playout turns that pick uniformly among all legal actions */
+} muz_dog_guided_cfg;
+/* The guided search of every game of `state` (read only) on `stream`, without a host synchronisation: the launches of
+ * muz_dog_rollout_search with the guided rollout kernel in the rollout kernel's place, and one memset when `decided`
+ * is given.  The workspace is muz_dog_rollout_search's (muz_dog_rollout_bytes).  decided[g] = the number of game g's
+ * rollouts whose outcome was not 0 (the playouts that carried signal: compare with the sum of visits).  All checks
+ * come before any launch: every check of muz_dog_rollout_search on cfg.rollout and the other arguments, MUZ_E_INVALID
+ * for a weight out of range and for an epsilon that is NaN, negative or above 1; n == 0 is MUZ_OK with nothing
+ * launched. */
+int muz_dog_guided_rollout_search(const muz_rules* rules /*host*/, const muz_dog_guided_cfg* cfg /*host*/,
+                                  muz_dog_soa state /* read only */, const int32_t* game_id /* null: 0..n-1 */,
+                                  int32_t* action, float* value, int32_t* visits /* [n][806], nullable */,
+                                  int32_t* wins /* [n][806], nullable */, uint32_t* rollout_turns /* [n], nullable */,
+                                  uint32_t* decided /* [n], nullable */, int32_t n, void* ws, int64_t ws_bytes,
+                                  void* stream);
+
 /* ---- MuZero networks (MuZero_det_MADN/muzero_deterministic_madn.py) --------------------------
  * Dense layers used by the MFMA kernels take their kernel W[K][N] PACKED for
  * v_mfma_f32_16x16x4_f32 B-fragments: [group][K/16][lane 64][tile NT][j 4] (group = wave, see muz_tile_waves) with
